@@ -17,7 +17,10 @@ step, the 112-byte state round trip and the 5 bytes of reward/done once per laun
 With N > 1 GPUs the drones are sharded contiguously (weak scaling: 2^20 per GPU) and each step's
 bit-packed done mask is all-gathered over RCCL, asynchronously, bucketed and double-buffered.
 
-Prints ONE JSON line on rank 0 (see the driver contract) with `roofline` and `cpu_baseline`.
+Prints ONE JSON line on rank 0 (see the driver contract) with `roofline`.  A plain run sets up, warms up, times the K steps
+and prints; `--full` adds the legs that take runs of their own (roofline.sustained / beyond_mall / launch_time_fit / xcd_map,
+the per-rank physics-only leg of an N-rank run) and `cpu_baseline`.  `--dump-outputs DIR` saves what the last timed step
+computed (a seeded sample of the drones) for comparing two builds output for output.
 """
 import argparse
 import hashlib
@@ -518,6 +521,14 @@ def parse_args(argv=None):
                     help="--api step only, N = 1: step the population as this many column partitions, each an independent kernel "
                          "chain on its own stream (FpvVecEnv.step_async / step_wait, the split-phase API a closed-loop caller can "
                          "use): the chains hide part of each other's per-launch floor.  A labelled line, not the headline")
+    ap.add_argument("--full", action="store_true",
+                    help="also run what the headline figure does not need: the sustained, beyond-MALL and launch-time-fit legs, the "
+                         "XCD-map probe, the physics-only leg of an N-rank run and the CPU baseline.  Off by default: a plain run "
+                         "sets up, warms up, times the K steps and prints its line")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, save what the timed path computed in its last step as DIR/<name>.npy (float32 / "
+                         "float64): every state row, reward and done of a fixed, seeded sample of at most 2^18 drones (per rank: "
+                         "2^18 / N, files suffixed _rank<r>) and the sampled drone indices.  Same arguments, same inputs")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-beyond-mall", action="store_true",
                     help="skip the extra short run at 2^23 drones (state 470 MB > the 256 MiB Infinity Cache)")
@@ -568,8 +579,8 @@ def parse_args(argv=None):
                     help="N > 1: what every attempt still in the plan keeps for itself (process start, import, rendezvous, the short run)")
     ap.add_argument("--pg-timeout-s", type=float, default=180.0, help="process-group timeout inside a worker: a rank whose peer died leaves its collective after this long")
     ap.add_argument("--sustained-steps", type=int, default=2000,
-                    help="N = 1, --api step: after the contract's K timed steps, this many more launches at the headline size, HIP-event "
-                         "timed (roofline.sustained): the steady state next to the driver's short shape; 0 = skip")
+                    help="N = 1, --api step, --full: after the contract's K timed steps, this many more launches at the headline size, "
+                         "HIP-event timed (roofline.sustained): the steady state next to the driver's short shape; 0 = skip")
     ap.add_argument("--stub-preflight", choices=["ok", "fail", "hang"], default="ok",
                     help="TEST ONLY (with --stub-step): what the preflight children do")
     ap.add_argument("--stub-fail-collective", choices=["", "rccl", "gloo", "all"], default="",
@@ -683,6 +694,30 @@ def run_stub(args, world, rank, collective="rccl"):
         dist.barrier()
         dist.destroy_process_group()
     return 0 if ok else 1
+
+
+DUMP_SAMPLE_DRONES = 1 << 18     # --dump-outputs: drones saved per job (16 MiB of fp32 state rows at 2^18)
+DUMP_SAMPLE_SEED = 20251016
+
+
+def dump_outputs(env, out_dir, rank=0, world=1):
+    """--dump-outputs: what a caller of the timed path holds after its last step - every state row (fp32 values; decoded for fp16
+    storage), reward and done - for a fixed, seeded sample of the drones (all of them when the shard is no larger than the
+    sample), as float32 .npy files, with the sampled drone indices (float64, shard-local).  The same arguments give the same sample."""
+    import numpy as np
+    import torch
+    n = env.n
+    k = min(n, max(1, DUMP_SAMPLE_DRONES // world))
+    idx = np.arange(n) if k == n else np.sort(np.random.default_rng(DUMP_SAMPLE_SEED).choice(n, size=k, replace=False))
+    sel = torch.from_numpy(idx).to(env.device)
+    arrays = {"state": env.rows_f32(0, env.rows).index_select(0, sel),          # [k, rows]: fpv_abi.h row order
+              "reward": env.reward.index_select(0, sel),
+              "done": env.done.index_select(0, sel).float()}
+    os.makedirs(out_dir, exist_ok=True)
+    sfx = "" if world == 1 else f"_rank{rank}"
+    for name, t in arrays.items():
+        np.save(os.path.join(out_dir, f"{name}{sfx}.npy"), np.ascontiguousarray(t.cpu().numpy(), dtype=np.float32))
+    np.save(os.path.join(out_dir, f"drone_index{sfx}.npy"), idx.astype(np.float64))
 
 
 def main(argv=None):
@@ -916,6 +951,8 @@ def main(argv=None):
         if rank == 0:        # [world, rows, words] masks of the bucket that holds the last step
             np.save(os.path.join(args.dump_gathered, "gathered_last_bucket.npy"), gather.result(last_t // args.gather_block).cpu().numpy())
         np.save(os.path.join(args.dump_gathered, f"state_rank{rank}.npy"), env.state.cpu().numpy())
+    if args.dump_outputs:                # before any --full leg steps the env further
+        dump_outputs(env, args.dump_outputs, rank, world)
 
     def timed_leg(e, acts, k, t_base, repeats=1, c_loop=False):
         """`repeats` x k more steps of the same kind on the launch stream, each repeat HIP-event timed, no exchange.
@@ -967,19 +1004,20 @@ def main(argv=None):
 
     physics_ms = None
     if multi:
-        # the physics alone, per rank, after the timed region: the mask goes back to the batch's own word row (a k-step
-        # launch must not keep writing rows of a bucket that is no longer being gathered)
-        env.set_done_bits_target(None)
-        k2 = max(args.gather_block, min(400, max(args.steps, 64)))
-        leg = timed_leg(env, actions, k2, args.warmup + args.steps)
-        physics_ms = leg["avg_launch_us"] * 1e-3 * leg["launches"] / k2
+        if args.full:
+            # the physics alone, per rank, after the timed region: the mask goes back to the batch's own word row (a k-step
+            # launch must not keep writing rows of a bucket that is no longer being gathered)
+            env.set_done_bits_target(None)
+            k2 = max(args.gather_block, min(400, max(args.steps, 64)))
+            leg = timed_leg(env, actions, k2, args.warmup + args.steps)
+            physics_ms = leg["avg_launch_us"] * 1e-3 * leg["launches"] / k2
         coll = collective_report(dist, world, rank, dev, gather, local_elapsed * 1e3 / args.steps, collective=collective, physics_ms=physics_ms)
 
     # the steady state beside the driver's short shape (20 timed launches are 0.5 ms: the clock also holds the first
     # launch's latency and the closing synchronise): the same env, the same ring, HIP events around `--sustained-steps`
     # further launches at the headline population
     sustained = None
-    aux_ok = rank == 0 and world == 1 and not multi and args.api == "step"
+    aux_ok = args.full and rank == 0 and world == 1 and not multi and args.api == "step"
     if aux_ok and args.sustained_steps > 0:
         leg = timed_leg(env, actions, args.sustained_steps, args.warmup + args.steps)
         us = leg["avg_launch_us"]
@@ -1146,7 +1184,7 @@ def main(argv=None):
                          "note": "avg_launch_us = HIP-event time over the timed region / launches (includes inter-launch gaps); achieved / frac follow `value` "
                                  "(wall clock), achieved_events / frac_events follow avg_launch_us - see frac_formula"},
         }
-        if world == 1 and args.api == "step":
+        if args.full and world == 1 and args.api == "step":
             out["roofline"]["xcd_map"] = xcd_map_probe(dev, int(_lib_step_grid(n)))
         if venv is not None:
             out["roofline"]["note"] = (f"split phase: one step = {venv.partitions} launches on {venv.partitions} streams that overlap; avg_launch_us is the "
@@ -1208,7 +1246,7 @@ def main(argv=None):
             else:
                 out["roofline"]["note"] = ("the k-step kernel is bound by vector-ALU issue, but no instruction count is on file for this "
                                            "configuration (valu_unavailable): the figures shown are the algorithmic-bytes (HBM) view; " + out["roofline"]["note"])
-        if not args.no_cpu_baseline and world == 1:
+        if args.full and not args.no_cpu_baseline and world == 1:
             out["cpu_baseline"] = cpu_baseline(params)
         print(json.dumps(out), flush=True)
     if multi:

@@ -125,7 +125,7 @@ def test_bench_line_schema_small(extra):
     import sys
     from conftest import REPO
     r = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--steps", "40", "--warmup", "8", "--drones-per-gpu", str(1 << 16),
-                        "--sustained-steps", "64", "--no-beyond-mall", "--preheat-s", "0.05", "--no-cpu-baseline"] + extra,
+                        "--sustained-steps", "64", "--no-beyond-mall", "--preheat-s", "0.05", "--no-cpu-baseline", "--full"] + extra,
                        capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.strip()]
@@ -151,6 +151,49 @@ def test_bench_line_schema_small(extra):
             assert d["config"]["partition_streams"]["verified"] is True
 
 
+def test_bench_plain_run_dumps_the_last_timed_step(tmp_path):
+    """bench.py without --full: the contract's keys, no auxiliary leg and no CPU baseline; --dump-outputs saves the last timed
+    step's state rows, reward and done (float32) with the drone indices.  Two runs with the same arguments write the same files
+    bit for bit, and the state is what warm-up + steps single steps of the same seeded sticks give."""
+    import json
+    import os
+    import subprocess
+    import sys
+    from conftest import REPO
+    from fpyv_amd.env import DroneBatch
+    n, steps, warm, ring = 1 << 14, 30, 6, 8
+    for run in ("a", "b"):
+        r = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--gpus", "1", "--steps", str(steps), "--warmup", str(warm),
+                            "--drones-per-gpu", str(n), "--ring", str(ring), "--preheat-s", "0.05", "--dump-outputs", str(tmp_path / run)],
+                           capture_output=True, text=True, timeout=600)
+        assert r.returncode == 0, r.stderr[-3000:]
+        lines = [ln for ln in r.stdout.splitlines() if ln.strip()]
+        assert len(lines) == 1, lines
+        d = json.loads(lines[0])
+        assert d["steps"] == steps and d["warmup"] == warm and d["ms_per_step"] > 0 and d["dtype"] == "f32" and d["higher_is_better"] is True
+        assert "cpu_baseline" not in d and "xcd_map" not in d["roofline"]
+        assert all(d["roofline"][k] is None for k in ("sustained", "beyond_mall", "launch_time_fit"))
+    names = sorted(os.listdir(tmp_path / "a"))
+    assert names == ["done.npy", "drone_index.npy", "reward.npy", "state.npy"] and sorted(os.listdir(tmp_path / "b")) == names
+    got = {}
+    for f in names:
+        a, b = np.load(tmp_path / "a" / f), np.load(tmp_path / "b" / f)
+        assert a.dtype in (np.float32, np.float64) and a.dtype == b.dtype and a.shape == b.shape
+        assert np.array_equal(a.view(np.uint8), b.view(np.uint8)), f
+        got[f[:-4]] = a
+    assert np.array_equal(got["drone_index"], np.arange(n, dtype=np.float64))           # a shard this small is saved whole
+    e = DroneBatch(load_params(fps=1000, ceiling=100.0), n, device=DEV, auto_reset=True, with_accel=False)
+    e.reset()
+    acts = sticks.ema_noise_device(ring, n, DEV, seed=1234)
+    for t in range(warm + steps):
+        e.step(acts[t % ring], return_imu=False)
+    torch.cuda.synchronize()
+    assert got["state"].shape == (n, e.rows)
+    assert np.array_equal(got["state"].view(np.uint32), e.state[:, :n].t().cpu().numpy().view(np.uint32))
+    assert np.array_equal(got["reward"].view(np.uint32), e.reward.cpu().numpy().view(np.uint32))
+    assert np.array_equal(got["done"], e.done.cpu().numpy().astype(np.float32))
+
+
 def test_bench_line_auxiliary_legs_at_the_headline_size():
     """The legs only the full-size line has: `beyond_mall` at 2^23 drones with its three repeats, host enqueue
     time and buffer addresses, and `launch_time_fit` over 3 * 2^18 / 2^20 / 2^21 drones (beyond the L2s, inside the Infinity Cache) with per-leg repeats, host enqueue time
@@ -161,7 +204,7 @@ def test_bench_line_auxiliary_legs_at_the_headline_size():
     import subprocess
     import sys
     from conftest import REPO
-    r = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--steps", "20", "--warmup", "5", "--sustained-steps", "200", "--no-cpu-baseline"],
+    r = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--steps", "20", "--warmup", "5", "--sustained-steps", "200", "--no-cpu-baseline", "--full"],
                        capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.strip()]

@@ -5,12 +5,15 @@ import os
 import numpy as np
 import pytest
 
-from conftest import load_golden
+from conftest import GOLDEN, load_golden
 from fpyv_amd import read_motor_test_report
 from fpyv_amd.params import ypr_to_quat, DEFAULT_PARAMS_PATH, params_from_dict
 
-REF_CSV = "/root/reference/config/t_motos_f80_motor_test.csv"
-REF_YAML = "/root/reference/config/params.yaml"
+# the reference's own config/params.yaml and raw motor test report, kept verbatim as fixtures (its report path is a
+# Windows path: the loader falls back to the file of that name beside the YAML)
+REF_DIR = os.path.join(GOLDEN, "reference_config")
+REF_CSV = os.path.join(REF_DIR, "t_motos_f80_motor_test.csv")
+REF_YAML = os.path.join(REF_DIR, "params.yaml")
 
 
 def test_thrust_curve_coefficients(params_1k):
@@ -64,7 +67,6 @@ def test_raw_vendor_format(tmp_path):
     np.testing.assert_array_equal(blocks[1]["throttle"], [50, 100])
 
 
-@pytest.mark.skipif(not os.path.isfile(REF_CSV), reason="reference mount not present (GPU box)")
 def test_reference_files_load_unchanged():
     """A reference params.yaml + raw CSV give the same constants as the packaged defaults."""
     g = load_golden("params_golden")

@@ -22,7 +22,7 @@ timeout -k 10 200 python3 tools/xcd_map_probe.py --out $O/xcd_map.json > $O/xcd_
 # counters first (they define traffic / VALU counts that the bench lines quote)
 timeout -k 10 300 rocprofv3 --kernel-trace --pmc SQ_INSTS_VALU SQ_INSTS_SALU SQ_WAVES --output-format csv -d $O/pmc_valu -- python3 tools/kernel_sweep.py --fp16 --racer --noise --extras --fused --rounds 1 --launches 64 --ring 32 > $O/pmc_valu.log 2>&1; echo "pmc valu rc=$?"
 python3 tools/pmc_valu.py $O/pmc_valu --steps-per-launch 32 --round $R > $O/valu_counts.log 2>&1; tail -2 $O/valu_counts.log
-timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof_kt -- python3 bench.py --steps 2000 --warmup 200 --no-cpu-baseline --no-beyond-mall > $O/prof_kt.log 2>&1; echo "kt rc=$?"
+timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof_kt -- python3 bench.py --steps 2000 --warmup 200 --no-cpu-baseline --no-beyond-mall --full > $O/prof_kt.log 2>&1; echo "kt rc=$?"
 timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof_kt_variants -- python3 tools/kernel_sweep.py --fp16 --noise --extras --racer --fused --rounds 2 > $O/prof_kt_variants.log 2>&1; echo "kt variants rc=$?"
 timeout -k 10 300 rocprofv3 --kernel-trace --pmc FETCH_SIZE --output-format csv -d $O/pmc_fetch -- python3 tools/pmc_probe.py > $O/pmc_fetch.log 2>&1; echo "fetch rc=$?"
 timeout -k 10 300 rocprofv3 --kernel-trace --pmc WRITE_SIZE --output-format csv -d $O/pmc_write -- python3 tools/pmc_probe.py > $O/pmc_write.log 2>&1; echo "write rc=$?"
@@ -35,21 +35,21 @@ cp profiles/pmc_traffic.json profiles/pmc_valu.json profiles/${R}_pmc_summary.md
 fi
 if [ "$STAGE" = counters ]; then exit 0; fi
 # bench lines: the headline (default K / W), the driver's shape, every other API / storage / variant
-T=500 run bench_step python bench.py
-run bench_step_20 python bench.py --steps 20 --warmup 5
+T=500 run bench_step python bench.py --full
+run bench_step_20 python bench.py --full --steps 20 --warmup 5
 for i in 1 2 3; do run bench_p1_20_$i python bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-beyond-mall --sustained-steps 0; run bench_p2_20_$i python bench.py --partitions 2 --steps 20 --warmup 5 --no-cpu-baseline --sustained-steps 0; done
-run bench_partitions2 python bench.py --partitions 2 --no-cpu-baseline
-run bench_rollout python bench.py --api rollout --no-cpu-baseline
-run bench_fp16 python bench.py --fp16-state --no-cpu-baseline
-run bench_fp16_rollout python bench.py --fp16-state --api rollout --no-cpu-baseline
-run bench_racerW python bench.py --racer written --no-cpu-baseline --steps 5000
-run bench_racerD python bench.py --racer omega_dt --no-cpu-baseline --steps 5000
-run bench_forcedist python bench.py --force-dist --no-cpu-baseline --steps 5000
-run bench_forcedist_20 python bench.py --force-dist --no-cpu-baseline --steps 20 --warmup 5
-T=400 run bench_rehearsal_2ranks python bench.py --gpus 2 --rehearse-on-one-gpu --steps 2000 --warmup 100 --no-cpu-baseline --drones-per-gpu 524288
+run bench_partitions2 python bench.py --full --partitions 2 --no-cpu-baseline
+run bench_rollout python bench.py --full --api rollout --no-cpu-baseline
+run bench_fp16 python bench.py --full --fp16-state --no-cpu-baseline
+run bench_fp16_rollout python bench.py --full --fp16-state --api rollout --no-cpu-baseline
+run bench_racerW python bench.py --full --racer written --no-cpu-baseline --steps 5000
+run bench_racerD python bench.py --full --racer omega_dt --no-cpu-baseline --steps 5000
+run bench_forcedist python bench.py --full --force-dist --no-cpu-baseline --steps 5000
+run bench_forcedist_20 python bench.py --full --force-dist --no-cpu-baseline --steps 20 --warmup 5
+T=400 run bench_rehearsal_2ranks python bench.py --full --gpus 2 --rehearse-on-one-gpu --steps 2000 --warmup 100 --no-cpu-baseline --drones-per-gpu 524288
 # the exact shape the driver launches at N = 2, both ranks on this one GPU over gloo: not a measurement, a rehearsal of the
 # ABI-8 tree at world size 2 - supervisor, preflight, collective budget, the line's schema
-T=400 run bench_rehearsal_2ranks_20 python bench.py --gpus 2 --rehearse-on-one-gpu --steps 20 --warmup 5
+T=400 run bench_rehearsal_2ranks_20 python bench.py --full --gpus 2 --rehearse-on-one-gpu --steps 20 --warmup 5
 # where the state matrix lands decides the launch time beyond the Infinity Cache: the spread inside one process
 timeout -k 10 300 python tools/beyond_placement.py combos 4 > $O/beyond_combos.log 2>&1; echo "combos rc=$?"
 timeout -k 10 300 python tools/beyond_placement.py sizes 5 > $O/beyond_sizes.log 2>&1; echo "sizes rc=$?"

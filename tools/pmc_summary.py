@@ -83,7 +83,7 @@ def main():
     with open(os.path.join(out_dir, f"{a.round}_pmc_summary.md"), "w") as f:
         f.write(f"# {a.round}: rocprofv3 summary of the step kernel (N = {a.n} drones, dt = 1 ms, EMA-noise sticks)\n\n")
         f.write("Commands (GPU box, one MI355X):\n\n```\n"
-                "rocprofv3 --kernel-trace --stats --output-format csv -d prof_kt -- python3 bench.py --steps 2000 --warmup 200 --no-cpu-baseline --no-beyond-mall\n"
+                "rocprofv3 --kernel-trace --stats --output-format csv -d prof_kt -- python3 bench.py --steps 2000 --warmup 200 --no-cpu-baseline --no-beyond-mall --full\n"
                 "rocprofv3 --kernel-trace --pmc FETCH_SIZE --output-format csv -d pmc_fetch -- python3 tools/pmc_probe.py\n"
                 "rocprofv3 --kernel-trace --pmc WRITE_SIZE --output-format csv -d pmc_write -- python3 tools/pmc_probe.py\n```\n\n")
         f.write("## kernel trace (--stats)\n\n| kernel | calls | avg ns | min ns | max ns |\n|---|---:|---:|---:|---:|\n")
