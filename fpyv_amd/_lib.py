@@ -13,7 +13,7 @@ from typing import Optional
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libfpv_hip.so")
 
-FPV_ABI_VERSION = 8
+FPV_ABI_VERSION = 9
 FPV_OK = 0
 FPV_MODE_DRONE, FPV_MODE_RACER = 0, 1
 FPV_DRONE_ROWS, FPV_RACER_ROWS = 14, 29
@@ -21,6 +21,8 @@ FPV_FLAG_AUTO_RESET = 1
 FPV_FLAG_GROUND = 2
 FPV_FLAG_FP16_STATE = 4
 FPV_FLAG_STICK_NOISE = 8
+FPV_FLAG_RESET_JITTER = 16
+RESET_POSE_ROWS = 10          # fpv_buffers_t.reset_pose: [10][ld] = p3 v3 q4 (wxyz), the state's row order
 FPV_HALF_PAIR_ROWS = 5
 FPV_HALF_HALVES = 11          # binary16 values per drone in state_h (5 pair rows + 1 half row)
 FPV_OBS_AOS_DIM = 16
@@ -35,7 +37,7 @@ EXPORTS = ("fpv_abi_version", "fpv_sizeof", "fpv_state_rows", "fpv_algorithmic_b
            "fpv_recommended_ld_device", "fpv_check_cache_model", "fpv_device_cache_model", "fpv_get_cache_model",
            "fpv_diag_stream_copy", "fpv_diag_stream_copy_wide", "fpv_diag_busy", "fpv_diag_xcd_map", "fpv_pid_reset", "fpv_pid_call", "fpv_comm_unique_id", "fpv_comm_create", "fpv_comm_destroy", "fpv_comm_info",
            "fpv_allgather_done", "fpv_allgather_f32", "fpv_last_error",
-           "fpv_error_name", "fpv_encoding_id")
+           "fpv_error_name", "fpv_encoding_id", "fpv_reset_pose_sample")
 
 
 class FpvParams(C.Structure):
@@ -57,6 +59,9 @@ class FpvParams(C.Structure):
         ("racer_pid_variant", C.c_uint32), ("_reserved0", C.c_uint32),
         ("pid_integral_clip", C.c_double), ("pid_min_output", C.c_double), ("pid_max_output", C.c_double),
         ("pid_derivative_transition_rate", C.c_double),
+        # ABI 9: FPV_FLAG_RESET_JITTER boxes ([lo row, hi row]) and seed
+        ("reset_pos_range", (C.c_double * 3) * 2), ("reset_vel_range", (C.c_double * 3) * 2),
+        ("reset_ypr_range_deg", (C.c_double * 3) * 2), ("reset_seed", C.c_uint64),
     ]
 
 
@@ -103,7 +108,7 @@ class FpvBuffers(C.Structure):
         ("wind", C.c_float * 3), ("rounding_seed", C.c_uint32), ("state_h", C.c_void_p),
         ("pos_comp", C.c_void_p), ("noise_state", C.c_void_p), ("action_out", C.c_void_p), ("action_ld", C.c_int64), ("objects", C.c_void_p), ("obs_aos", C.c_void_p),
         ("done_bits_stride", C.c_int64), ("rotation_override", C.c_void_p), ("thrust_override", C.c_void_p),
-        ("state_h_thrust", C.c_void_p),
+        ("state_h_thrust", C.c_void_p), ("reset_pose", C.c_void_p),
     ]
 
 
@@ -145,6 +150,18 @@ def pack_params(p, auto_reset: bool = False, fp16_state: bool = False, stick_noi
     s.pid_max_output = float(getattr(p, "pid_max_output", 1.0))
     s.pid_derivative_transition_rate = float(getattr(p, "pid_derivative_transition_rate", 0.5))
     s.motor_radius, s.ground_spring, s.ground_damping = float(p.motor_radius), float(p.ground_spring), float(p.ground_damping)
+    # reset jitter (ABI 9): any box that is set turns the flag on; a box left at None is [0, 0]
+    boxes = [getattr(p, "reset_position_range", None), getattr(p, "reset_velocity_range", None), getattr(p, "reset_ypr_range_deg", None)]
+    if any(b is not None for b in boxes):
+        s.flags |= FPV_FLAG_RESET_JITTER
+        for dst, box in zip((s.reset_pos_range, s.reset_vel_range, s.reset_ypr_range_deg), boxes):
+            if box is not None:
+                rows = [[float(x) for x in row] for row in box]
+                if len(rows) != 2 or any(len(r) != 3 for r in rows):
+                    raise ValueError("a reset range is [2, 3]: a lo row and a hi row of three components")
+                for r in range(2):
+                    dst[r][:] = rows[r]
+    s.reset_seed = int(getattr(p, "reset_seed", 0)) & (2 ** 64 - 1)
     return s
 
 
@@ -226,6 +243,7 @@ def lib() -> C.CDLL:
     L.fpv_encoding_id.argtypes = [C.c_int]
     L.fpv_encoding_id.restype = C.c_char_p
     L.fpv_sizeof.argtypes = [C.c_int]
+    L.fpv_reset_pose_sample.argtypes = [pp, C.c_uint64, C.c_uint64, C.c_int, vp, vp]
     if L.fpv_abi_version() != FPV_ABI_VERSION:
         raise ImportError(f"libfpv_hip.so ABI {L.fpv_abi_version()} != binding {FPV_ABI_VERSION} - rebuild the library "
                           "(`python -c 'import __graft_entry__ as g; g.build()'`)")

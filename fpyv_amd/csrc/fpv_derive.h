@@ -25,6 +25,7 @@ static inline int fpv_derive_constants(const fpv_params_t* P, FpvK* K, const cha
     if ((P->flags & FPV_FLAG_FP16_STATE) && P->mode != FPV_MODE_DRONE) { *why = "FPV_FLAG_FP16_STATE is a drone-mode layout"; return FPV_EINVAL; }
     if ((P->flags & FPV_FLAG_STICK_NOISE) && (P->mode != FPV_MODE_DRONE || (P->flags & FPV_FLAG_FP16_STATE))) { *why = "FPV_FLAG_STICK_NOISE needs drone mode with fp32 state"; return FPV_EINVAL; }
     if ((P->flags & FPV_FLAG_STICK_NOISE) && !(P->noise_transition > 0 && P->noise_transition <= 1)) { *why = "noise_transition must be in (0, 1]"; return FPV_EPARAM; }
+    if ((P->flags & FPV_FLAG_RESET_JITTER) && P->mode != FPV_MODE_DRONE) { *why = "FPV_FLAG_RESET_JITTER is a drone-mode reset source (the Racer resets to its zero state)"; return FPV_EINVAL; }
     if (!(P->dt > 0) || !isfinite(P->dt)) { *why = "dt must be positive and finite"; return FPV_EPARAM; }
     if (!(P->mass > 0)) { *why = "mass must be positive"; return FPV_EPARAM; }
     if (!(P->max_rates >= 0) || !isfinite(P->max_rates)) { *why = "max_rates must be finite and >= 0"; return FPV_EPARAM; }
@@ -128,5 +129,25 @@ static inline int fpv_derive_constants(const fpv_params_t* P, FpvK* K, const cha
     // polynomials, beyond that the angle is reduced first (fpv_sincos3)
     const double half_max = 0.5 * (M_PI / 180.0) * P->dt * P->max_rates;
     K->angle_mode = half_max <= 0.03 ? FPV_ANGLE_TINY : half_max <= 0.78 ? FPV_ANGLE_SMALL : FPV_ANGLE_REDUCED;
+    return FPV_OK;
+}
+
+// FPV_FLAG_RESET_JITTER: the three boxes narrowed to fp32 as lo and span = hi - lo (span in double, then narrowed: a box that
+// straddles zero keeps its width); zeros without the flag.  Returns 0 or FPV_EPARAM (non-finite bound, lo > hi).
+static inline int fpv_derive_reset_jitter(const fpv_params_t* P, FpvResetJitter* J, const char** why)
+{
+    *why = "";
+    memset(J, 0, sizeof(*J));
+    if (!(P->flags & FPV_FLAG_RESET_JITTER)) return FPV_OK;
+    const double (*box[3])[3] = {P->reset_pos_range, P->reset_vel_range, P->reset_ypr_range_deg};
+    for (int b = 0; b < 3; ++b)
+        for (int c = 0; c < 3; ++c) {
+            const double lo = box[b][0][c], hi = box[b][1][c];
+            if (!isfinite(lo) || !isfinite(hi)) { *why = "reset_*_range bounds must be finite"; return FPV_EPARAM; }
+            if (lo > hi) { *why = "reset_*_range: lo > hi"; return FPV_EPARAM; }
+            J->lo[3 * b + c] = (float)lo;
+            J->span[3 * b + c] = (float)(hi - lo);
+        }
+    J->seed_lo = (uint32_t)P->reset_seed; J->seed_hi = (uint32_t)(P->reset_seed >> 32);
     return FPV_OK;
 }

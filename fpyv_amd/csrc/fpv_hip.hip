@@ -68,6 +68,9 @@ struct FpvBufD {
     const float* rot_over;     // [n][9] guidance override of the attitude (Drone.step rotation_matrix=) or null
     const float* thrust_over;  // [n] thrust_force= of the same call (NaN = this drone is not overridden)
     uint16_t* thrust_h;        // FPV_FLAG_FP16_STATE: the row of prev_thrust halves (always set by to_device_view)
+    // reset sources (fpv_abi.h, ABI 9) - last, so that no field the hot kernels read moves; read only inside the reset branch
+    const float* reset_pose;   // [10][ld] per-lane base pose (p3 v3 q4) or null
+    FpvResetJitter rj;         // FPV_FLAG_RESET_JITTER: the narrowed boxes and the seed (zeros without the flag)
 };
 
 // k-step launches (fpv_step_n): step t reads its action at + t*action_stride floats and writes
@@ -158,6 +161,23 @@ __device__ __forceinline__ void emit_lane_outputs(const FpvBufD& B, uint32_t i, 
         B.ep_return[i] = done ? 0.0f : r;
         B.ep_length[i] = done ? 0 : l;
     }
+}
+
+// Reset sources (fpv_abi.h): after fpv_drone_reset_lane has put init_* into `s`, a lane that resets takes its base pose from
+// its row of the reset-pose table, when there is one, and adds the jitter of FPV_FLAG_RESET_JITTER.  Only the rare reset branch
+// of the kernels that are not on the headline path calls this, with the view of the arguments it loads inside the branch.
+// `t` = step index of the step whose done started the reset (fpv_reset: the handle's counter), `e` = 1 for fpv_reset.
+__device__ __forceinline__ void apply_reset_source(const FpvK& K, const FpvBufD& B, uint32_t i, uint64_t t, uint32_t e, FpvDroneState& s)
+{
+    float pose[10] = {s.px, s.py, s.pz, s.vx, s.vy, s.vz, s.q.w, s.q.x, s.q.y, s.q.z};
+    if (B.reset_pose) {
+#pragma unroll
+        for (int r = 0; r < 10; ++r) pose[r] = row_at(ROW(B.reset_pose, r, B.ld), i);
+    }
+    if (K.flags & FPV_FLAG_RESET_JITTER)
+        fpv_reset_jitter(B.rj, (((uint64_t)K.noise.id_hi << 32) | K.noise.id_lo) + i, t, e, pose);
+    s.px = pose[0]; s.py = pose[1]; s.pz = pose[2]; s.vx = pose[3]; s.vy = pose[4]; s.vz = pose[5];
+    s.q.w = pose[6]; s.q.x = pose[7]; s.q.y = pose[8]; s.q.z = pose[9];
 }
 
 // "These values are used here": makes the compiler complete the loads that produced them BEFORE a k-step
@@ -396,6 +416,42 @@ __device__ __forceinline__ const FpvRollArgs& fpv_args_again()
     return *(const FpvRollArgs*)p;
 }
 
+// The reset sources of a k-step kernel's reset branch (apply_reset_source for the k-step kernels).  Their SGPR files are spoken for
+// by the loop: with the whole FpvResetJitter read through one view (apply_reset_source) 4-26 SGPRs spilled into VGPR lanes, and
+// read through a VGPR copy of the argument pointer the plain k-step kernel went from 56 to 90+ VGPRs.  Here each block's six
+// constants and key come through a view of their own that is ordered after the previous block's result: one block's uniforms are
+// live at a time (no spill; VGPRs within 2 of the kernels without the branch).
+__device__ __forceinline__ FpvArgsPtr fpv_args_after(float after)
+{
+    FpvArgsPtr p = (FpvArgsPtr)__builtin_amdgcn_kernarg_segment_ptr();
+    asm volatile("" : "+s"(p) : "v"(after));         // (ordered after `after`: one block's constants are loaded at a time)
+    return p;
+}
+
+__device__ __forceinline__ void apply_reset_source_k(uint32_t i, uint64_t t, FpvDroneState& s)
+{
+    float pose[10] = {s.px, s.py, s.pz, s.vx, s.vy, s.vz, s.q.w, s.q.x, s.q.y, s.q.z};
+    FpvArgsPtr A = fpv_args_after(s.px);
+    const float* tab = A->B.reset_pose;
+    if (tab) {
+        const int64_t ld = A->B.ld;
+#pragma unroll
+        for (int r = 0; r < 10; ++r) pose[r] = row_at(ROW(tab, r, ld), i);
+    }
+    if (A->K.flags & FPV_FLAG_RESET_JITTER) {
+#pragma unroll
+        for (uint32_t b = 0; b < 3; ++b) {
+            const FpvArgsPtr V = fpv_args_after(pose[3 * b]);
+            const float lo[3] = {V->B.rj.lo[3 * b], V->B.rj.lo[3 * b + 1], V->B.rj.lo[3 * b + 2]};
+            const float span[3] = {V->B.rj.span[3 * b], V->B.rj.span[3 * b + 1], V->B.rj.span[3 * b + 2]};
+            fpv_reset_jitter_block(lo, span, V->B.rj.seed_lo, V->B.rj.seed_hi, (((uint64_t)V->K.noise.id_hi << 32) | V->K.noise.id_lo) + i,
+                                   V->B.step + t, 0u, b, pose);
+        }
+    }
+    s.px = pose[0]; s.py = pose[1]; s.pz = pose[2]; s.vx = pose[3]; s.vy = pose[4]; s.vz = pose[5];
+    s.q.w = pose[6]; s.q.x = pose[7]; s.q.y = pose[8]; s.q.z = pose[9];
+}
+
 // k steps of Drone.step in ONE launch (fpv_step_n): the loop `for i in range(time_steps): drone.step(...)`
 // of src/core/simulator.py:83-156 for pre-computed or in-kernel-generated sticks.  The lane keeps its
 // drone (and the noise / Kahan rows) in registers for all k steps; step t+1's action is in flight while
@@ -423,7 +479,10 @@ __global__ __launch_bounds__(kStepBlock) void fpv_drone_rollout_kernel(const Fpv
     FpvDroneState s;
     const int k = A.R.k;
     const bool has_action = !NOISE || A.B.action;
-    float4 a_next = has_action ? ld_action(A.B.action, i) : make_float4(0.f, 0.f, 0.f, 0.f);     // rows only (fpv_step_n)
+    // rows only for fpv_step_n; the k = 1 launches a reset-source handle's fpv_step is routed to (choose_kernel) may carry SoA sticks
+    float4 a_next = make_float4(0.f, 0.f, 0.f, 0.f);
+    if constexpr (SQ) { if (has_action) a_next = ld_action(A.B.action, i); }
+    else { if (has_action) a_next = ld_action_any(A.B.action, A.B.action_ld, i); }
     ld_drone(A.B.state, A.B.ld, i, s);
     float ns[4] = {0.f, 0.f, 0.f, 0.f}, kc[6] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
     if (NOISE) {
@@ -463,6 +522,8 @@ __global__ __launch_bounds__(kStepBlock) void fpv_drone_rollout_kernel(const Fpv
             // rare (once per episode and lane): the reset pose comes through its own view, inside the branch
             const FpvRollArgs& Z = fpv_args_again();
             fpv_drone_reset_lane(Z.K, s);
+            // (never launched for a handle with a reset source: the SQ bodies stay as they were)
+            if constexpr (!SQ) apply_reset_source_k(i, (uint64_t)t, s);
             if (KAHAN) {
 #pragma unroll
                 for (int c = 0; c < 6; ++c) kc[c] = 0.0f;
@@ -557,7 +618,10 @@ __global__ __launch_bounds__(kStepBlock) void fpv_drone_step_aos_kernel(FPV_STEP
         if (B.accel) {
             ST_OUT(row_at(ROW(B.accel, 0, B.ld), i), o.ax); ST_OUT(row_at(ROW(B.accel, 1, B.ld), i), o.ay); ST_OUT(row_at(ROW(B.accel, 2, B.ld), i), o.az);
         }
-        if ((K.flags & FPV_FLAG_AUTO_RESET) && o.done) fpv_drone_reset_lane(K, s);
+        if ((K.flags & FPV_FLAG_AUTO_RESET) && o.done) {
+            fpv_drone_reset_lane(K, s);
+            apply_reset_source(K, B, i, B.step, 0u, s);
+        }
         st_drone(B.state, B.ld, i, s);
         float* row = &tile[wave][lane * kPitch];
         row[0] = s.px; row[1] = s.py; row[2] = s.pz; row[3] = s.vx; row[4] = s.vy; row[5] = s.vz;
@@ -686,6 +750,7 @@ __global__ __launch_bounds__(kStepBlock) void fpv_drone_rollout_h_kernel(const F
         if ((V.K.flags & FPV_FLAG_AUTO_RESET) && o.done) {
             const FpvRollArgs& Z = fpv_args_again();
             fpv_drone_reset_lane(Z.K, s);
+            apply_reset_source_k(i, (uint64_t)t, s);
         }
         const FpvRollArgs& PV = fpv_args_again();             // the rounding's three uniforms, read where they are used
         fpv_pack_half(s, fpv_round_seed(PV.B.seed, PV.B.step + (uint64_t)t), PV.K.noise.id_lo + (uint32_t)i, h);   // the HBM round trip of a single step, in registers
@@ -884,9 +949,26 @@ __global__ __launch_bounds__(kBlock) void fpv_reset_kernel(const FpvK K, const F
     if (mode == FPV_MODE_DRONE) {
         FpvDroneState s;
         fpv_drone_reset_lane(K, s);
+        float* tab = const_cast<float*>(B.reset_pose);
+        if (tab) {      // the lane's own start (fpv_abi.h "Reset sources"): its table row, replaced where arguments are given
+            s.px = tab[0 * B.ld + i]; s.py = tab[1 * B.ld + i]; s.pz = tab[2 * B.ld + i];
+            s.vx = tab[3 * B.ld + i]; s.vy = tab[4 * B.ld + i]; s.vz = tab[5 * B.ld + i];
+            s.q.w = tab[6 * B.ld + i]; s.q.x = tab[7 * B.ld + i]; s.q.y = tab[8 * B.ld + i]; s.q.z = tab[9 * B.ld + i];
+        }
         if (pos) { s.px = pos[3 * i]; s.py = pos[3 * i + 1]; s.pz = pos[3 * i + 2]; }
         if (vel) { s.vx = vel[3 * i]; s.vy = vel[3 * i + 1]; s.vz = vel[3 * i + 2]; }
         if (ypr) s.q = fpv_quat_from_rpy_deg(ypr[3 * i], ypr[3 * i + 1], ypr[3 * i + 2]);
+        if (tab && (pos || vel || ypr)) {
+            tab[0 * B.ld + i] = s.px; tab[1 * B.ld + i] = s.py; tab[2 * B.ld + i] = s.pz;
+            tab[3 * B.ld + i] = s.vx; tab[4 * B.ld + i] = s.vy; tab[5 * B.ld + i] = s.vz;
+            tab[6 * B.ld + i] = s.q.w; tab[7 * B.ld + i] = s.q.x; tab[8 * B.ld + i] = s.q.y; tab[9 * B.ld + i] = s.q.z;
+        }
+        if (K.flags & FPV_FLAG_RESET_JITTER) {
+            float pose[10] = {s.px, s.py, s.pz, s.vx, s.vy, s.vz, s.q.w, s.q.x, s.q.y, s.q.z};
+            fpv_reset_jitter(B.rj, (((uint64_t)K.noise.id_hi << 32) | K.noise.id_lo) + (uint64_t)i, B.step, 1u, pose);
+            s.px = pose[0]; s.py = pose[1]; s.pz = pose[2]; s.vx = pose[3]; s.vy = pose[4]; s.vz = pose[5];
+            s.q.w = pose[6]; s.q.x = pose[7]; s.q.y = pose[8]; s.q.z = pose[9];
+        }
         if (K.flags & FPV_FLAG_FP16_STATE) {
             // masked lanes are independent here, so the thrust half goes out as a 2-byte store (not a hot path)
             const uint32_t th = st_drone_h(B, (uint32_t)i, K.noise.id_lo, B.seed, s);
@@ -1045,6 +1127,7 @@ struct fpv_env {
     int64_t n;
     int device;
     int mode;
+    FpvResetJitter rj;   // FPV_FLAG_RESET_JITTER constants (fpv_derive_reset_jitter), copied into every launch's FpvBufD
     uint64_t launches;   // 64-bit step index: counts the steps launched so far; keys the stick-noise stream (Philox
                          // counter words 2 and 3) and the stochastic rounding (fpv_round_seed)
     // rotation of the single-step kernels' start block (FPV_STEP_INDEX): blocks the start moves back per launch
@@ -1121,6 +1204,12 @@ int check_buffers(const fpv_env* h, const fpv_buffers_t* b, bool need_action)  /
         if (((uintptr_t)b->rotation_override & 3) || ((uintptr_t)b->thrust_override & 3))
             return fail(FPV_EALIGN, "rotation_override / thrust_override must be 4-byte aligned");
     }
+    if (b->reset_pose || (h->K.flags & FPV_FLAG_RESET_JITTER)) {
+        if (h->mode != FPV_MODE_DRONE) return fail(FPV_EINVAL, "reset sources (reset_pose, FPV_FLAG_RESET_JITTER) are drone-mode only");
+        if (b->rotation_override) return fail(FPV_EINVAL, "the guidance override cannot be combined with a reset source (reset_pose / FPV_FLAG_RESET_JITTER)");
+        if ((uintptr_t)b->reset_pose & 15) return fail(FPV_EALIGN, "reset_pose must be 16-byte aligned");
+        if (b->reset_pose && b->ld < h->n) return fail(FPV_EALIGN, "fpv_buffers_t.ld is smaller than the number of drones");
+    }
     if ((b->ep_return == nullptr) != (b->ep_length == nullptr))
         return fail(FPV_EINVAL, "ep_return and ep_length must be given together");
     if ((b->last_return || b->last_length) && !b->ep_return)
@@ -1128,9 +1217,10 @@ int check_buffers(const fpv_env* h, const fpv_buffers_t* b, bool need_action)  /
     return FPV_OK;
 }
 
-// `reach` = the handle's K.contact_reach: the bounds of the object list are grown by it (fpv_objects_bounds)
-FpvBufD to_device_view(const fpv_buffers_t* b, float reach)
+// the bounds of the object list are grown by the handle's K.contact_reach (fpv_objects_bounds)
+FpvBufD to_device_view(const fpv_env* h, const fpv_buffers_t* b)
 {
+    const float reach = h->K.contact_reach;
     FpvBufD d;
     memset(&d, 0, sizeof(d));          // padding bytes are part of the graph-cache key
     d.state = b->state; d.ld = b->ld; d.action = reinterpret_cast<const float4*>(b->action);
@@ -1154,6 +1244,8 @@ FpvBufD to_device_view(const fpv_buffers_t* b, float reach)
         }
         fpv_objects_bounds(d.objs, reach);
     }
+    d.reset_pose = b->reset_pose;
+    d.rj = h->rj;
     return d;
 }
 
@@ -1180,7 +1272,9 @@ struct DeviceGuard {
 
 // ---- kernel selection: every step kernel has the signature FPV_STEP_PARAMS ------------------------------
 typedef void (*StepKernel)(float*, const int64_t, const float4*, const int64_t, uint16_t*, const int64_t, const FpvK, const FpvBufD);
-struct KernelChoice { StepKernel func; unsigned grid, block; };
+typedef void (*RollKernel)(const FpvRollArgs);
+// func = a single-step kernel (FPV_STEP_PARAMS), or null and roll = a k-step kernel launched with k = 1 (reset sources, below)
+struct KernelChoice { StepKernel func; unsigned grid, block; RollKernel roll; };
 // blocks of one single-step launch: n's, in whole rounds of the eight XCDs (FPV_STEP_INDEX computes the same number from n)
 inline int64_t step_grid(int64_t n) { return (n + 8 * kStepBlock - 1) / (8 * kStepBlock) * 8; }
 
@@ -1207,7 +1301,6 @@ StepKernel racer_kernel(bool wide, bool pidv)
 }
 
 // ---- k-step kernels (fpv_step_n): one FpvRollArgs parameter ----
-typedef void (*RollKernel)(const FpvRollArgs);
 
 RollKernel drone_rollout_kernel(bool noise, bool obj, bool kahan, bool sq)
 {
@@ -1223,6 +1316,23 @@ RollKernel drone_rollout_kernel(bool noise, bool obj, bool kahan, bool sq)
     }
 }
 
+// Reset sources (fpv_abi.h: the reset-pose table, FPV_FLAG_RESET_JITTER) live in the rare reset branch of the kernels that are
+// NOT on the headline path: the non-SQ k-step kernels, the fp16 k-step kernel, the AoS-head kernel and the reset kernel.  The
+// plain and fp16 single-step kernels and the SQ k-step kernel stay exactly as they were (tests/test_isa_claims.py pins them), so
+// a handle with a reset source is routed around them:
+//   - its single-step launches (fpv_step, every launch of fpv_rollout) run the k-step kernel with k = 1 - the same lane function
+//     in the same order, bit-identical to the single-step kernel - fp32 state on fpv_drone_rollout_kernel (never SQ),
+//     fp16 state on fpv_drone_rollout_h_kernel; they do not rotate their traversal;
+//   - launches with the AoS head keep fpv_drone_step_aos_kernel, which carries the branch itself (the k-step kernel writes no
+//     obs_aos rows);
+//   - fpv_step_n never picks SQ; fpv_rollout_graph issues the launches instead of replaying them (the jitter needs the step
+//     index of every launch).
+// Cost: DESIGN.md "Reset sources".
+bool has_reset_source(const fpv_env* h, const FpvBufD& d)
+{
+    return h->mode == FPV_MODE_DRONE && (d.reset_pose != nullptr || (h->K.flags & FPV_FLAG_RESET_JITTER) != 0);
+}
+
 RollKernel choose_rollout_kernel(const fpv_env* h, const FpvBufD& d)
 {
     if (h->mode != FPV_MODE_DRONE) {
@@ -1232,7 +1342,8 @@ RollKernel choose_rollout_kernel(const fpv_env* h, const FpvBufD& d)
     }
     if (h->K.flags & FPV_FLAG_FP16_STATE) return fpv_drone_rollout_h_kernel;
     const bool noise = (h->K.flags & FPV_FLAG_STICK_NOISE) != 0, obj = d.objs.count > 0, kahan = d.pos_comp != nullptr;
-    const bool sq = !obj && h->K.motor_square && !(h->K.flags & FPV_FLAG_GROUND);      // X frame, no ground springs
+    const bool sq = !obj && h->K.motor_square && !(h->K.flags & FPV_FLAG_GROUND)      // X frame, no ground springs
+                    && !has_reset_source(h, d);                                          // (the SQ bodies carry no reset source)
     return drone_rollout_kernel(noise, obj, kahan, sq);
 }
 
@@ -1240,6 +1351,13 @@ KernelChoice choose_kernel(const fpv_env* h, const FpvBufD& d)
 {
     KernelChoice c;
     c.block = (unsigned)kStepBlock;
+    c.roll = nullptr;
+    if (has_reset_source(h, d) && !d.obs_aos) {          // routed around the pinned single-step kernels (see has_reset_source)
+        c.func = nullptr;
+        c.roll = choose_rollout_kernel(h, d);
+        c.grid = (unsigned)((h->n + kStepBlock - 1) / kStepBlock);
+        return c;
+    }
     if (h->mode != FPV_MODE_DRONE) {
         c.func = racer_kernel(h->K.r_wide != 0, h->K.r_pid_variant != 0);
     } else if (h->K.flags & FPV_FLAG_FP16_STATE) {
@@ -1264,6 +1382,18 @@ int launch_step(fpv_env* h, const FpvBufD& d_in, hipStream_t s)
     FpvBufD d = d_in;
     d.step = h->launches;
     const KernelChoice c = choose_kernel(h, d);
+    if (c.roll) {
+        // one step of the k-step kernel: reward / done / done_bits / episode sums leave after it, as after a single step
+        FpvRollArgs args;
+        memset(&args, 0, sizeof(args));
+        args.K = h->K; args.B = d; args.n = h->n;
+        args.R.k = 1; args.R.bits_stride = 0;
+        hipLaunchKernelGGL(c.roll, dim3(c.grid), dim3(c.block), 0, s, args);
+        const hipError_t e = hipGetLastError();
+        if (e != hipSuccess) return hip_fail(e, "step kernel launch");
+        ++h->launches;
+        return FPV_OK;
+    }
     const int64_t nblk = (int64_t)c.grid;
     h->rot_blocks = rotation_blocks(h, &d);
     const int64_t start = h->rot_blocks > 0 ? h->start_block % nblk : 0;
@@ -1495,15 +1625,17 @@ int fpv_create(const fpv_params_t* params, int64_t n, int device, fpv_handle_t* 
     *out = nullptr;
     if (n <= 0) return fail(FPV_EINVAL, "n must be positive");
     if (n > FPV_MAX_DRONES) return fail(FPV_EINVAL, "n exceeds 2^28 drones per handle (32-bit lane byte offsets into 16-byte action rows); split the population over handles");
+    FpvK K;
+    FpvResetJitter J;
+    const char* why = "";
+    int rc = fpv_derive_constants(params, &K, &why);
+    if (rc == FPV_OK) rc = fpv_derive_reset_jitter(params, &J, &why);
+    if (rc != FPV_OK) return fail(rc, why);
     const int drc = check_device_index(device);
     if (drc != FPV_OK) return drc;
-    FpvK K;
-    const char* why = "";
-    const int rc = fpv_derive_constants(params, &K, &why);
-    if (rc != FPV_OK) return fail(rc, why);
     fpv_env* h = new (std::nothrow) fpv_env;
     if (!h) return fail(FPV_EINVAL, "out of host memory");
-    h->K = K; h->P = *params; h->n = n; h->device = device; h->mode = (int)params->mode;
+    h->K = K; h->rj = J; h->P = *params; h->n = n; h->device = device; h->mode = (int)params->mode;
     h->launches = 0;
     const int mrc = device_cache_model(device, &h->cache);
     if (mrc != FPV_OK) { delete h; return mrc; }
@@ -1527,10 +1659,12 @@ int fpv_set_params(fpv_handle_t h, const fpv_params_t* params)
     if ((params->flags ^ h->P.flags) & (FPV_FLAG_FP16_STATE | FPV_FLAG_STICK_NOISE))
         return fail(FPV_EINVAL, "FPV_FLAG_FP16_STATE / FPV_FLAG_STICK_NOISE cannot change on a live handle (buffer layout differs)");
     FpvK K;
+    FpvResetJitter J;
     const char* why = "";
-    const int rc = fpv_derive_constants(params, &K, &why);
+    int rc = fpv_derive_constants(params, &K, &why);
+    if (rc == FPV_OK) rc = fpv_derive_reset_jitter(params, &J, &why);
     if (rc != FPV_OK) return fail(rc, why);
-    h->K = K; h->P = *params;
+    h->K = K; h->rj = J; h->P = *params;
     return FPV_OK;
 }
 
@@ -1572,6 +1706,21 @@ int fpv_get_cache_model(fpv_handle_t h, fpv_cache_model_t* out)
 {
     if (!h || !out) return fail(FPV_EINVAL, "null argument");
     *out = h->cache;
+    return FPV_OK;
+}
+
+int fpv_reset_pose_sample(const fpv_params_t* params, uint64_t global_id, uint64_t step, int explicit_reset,
+                          const float base[10], float out[10])
+{
+    if (!params || !base || !out) return fail(FPV_EINVAL, "null argument");
+    FpvK K;
+    FpvResetJitter J;
+    const char* why = "";
+    int rc = fpv_derive_constants(params, &K, &why);
+    if (rc == FPV_OK) rc = fpv_derive_reset_jitter(params, &J, &why);
+    if (rc != FPV_OK) return fail(rc, why);
+    for (int r = 0; r < 10; ++r) out[r] = base[r];
+    if (K.flags & FPV_FLAG_RESET_JITTER) fpv_reset_jitter(J, global_id, step, explicit_reset ? 1u : 0u, out);
     return FPV_OK;
 }
 
@@ -1634,7 +1783,9 @@ int fpv_reset(fpv_handle_t h, const fpv_buffers_t* b, const uint8_t* mask, const
     const DeviceGuard dev(h->device);
     if (dev.rc != FPV_OK) return dev.rc;
     const dim3 grid((unsigned)((h->n + kBlock - 1) / kBlock));
-    hipLaunchKernelGGL(fpv_reset_kernel, grid, dim3(kBlock), 0, (hipStream_t)stream, h->K, to_device_view(b, h->K.contact_reach),
+    FpvBufD d = to_device_view(h, b);
+    d.step = h->launches;                // the jitter of an explicit reset is keyed by the handle's step counter
+    hipLaunchKernelGGL(fpv_reset_kernel, grid, dim3(kBlock), 0, (hipStream_t)stream, h->K, d,
                        h->mode, mask, position, velocity, ypr_deg, h->n);
     const hipError_t e = hipGetLastError();
     if (e != hipSuccess) return hip_fail(e, "reset kernel launch");
@@ -1647,7 +1798,7 @@ int fpv_step(fpv_handle_t h, const fpv_buffers_t* b, void* stream)
     if (rc != FPV_OK) return rc;
     const DeviceGuard dev(h->device);
     if (dev.rc != FPV_OK) return dev.rc;
-    return launch_step(h, to_device_view(b, h->K.contact_reach), (hipStream_t)stream);
+    return launch_step(h, to_device_view(h, b), (hipStream_t)stream);
 }
 
 int fpv_rollout(fpv_handle_t h, const fpv_buffers_t* b, int k, int64_t action_stride, int64_t out_stride,
@@ -1660,7 +1811,7 @@ int fpv_rollout(fpv_handle_t h, const fpv_buffers_t* b, int k, int64_t action_st
     if (b->rotation_override) return fail(FPV_EINVAL, "the guidance override is a per-step input: use fpv_step");
     const DeviceGuard dev(h->device);
     if (dev.rc != FPV_OK) return dev.rc;
-    FpvBufD d = to_device_view(b, h->K.contact_reach);
+    FpvBufD d = to_device_view(h, b);
     const float* a0 = b->action;
     for (int t = 0; t < k; ++t) {
         d.action = a0 ? reinterpret_cast<const float4*>(a0 + (int64_t)t * action_stride) : nullptr;
@@ -1733,7 +1884,7 @@ int fpv_step_n(fpv_handle_t h, const fpv_buffers_t* b, int k, int64_t action_str
     if (b->rotation_override) return fail(FPV_EINVAL, "the guidance override is a per-step input: use fpv_step");
     const DeviceGuard dev(h->device);
     if (dev.rc != FPV_OK) return dev.rc;
-    FpvBufD d = to_device_view(b, h->K.contact_reach);
+    FpvBufD d = to_device_view(h, b);
     d.step = h->launches;
     FpvRoll R;
     R.k = k; R.pad = 0; R.action_stride = action_stride; R.out_stride = out_stride; R.bits_stride = b->done_bits_stride;
@@ -1786,9 +1937,13 @@ int fpv_rollout_graph(fpv_handle_t h, const fpv_buffers_t* b, int k, int64_t act
     // a graph replays frozen kernel arguments, but stick noise and the fp16 rounding are keyed by the per-launch step
     // index: such handles take the k-step kernel instead - the same k steps bit for bit, and cheaper than the replay
     if (h->K.flags & (FPV_FLAG_STICK_NOISE | FPV_FLAG_FP16_STATE)) return fpv_step_n(h, b, k, action_stride, out_stride, stream);
+    // the same for a reset source (the jitter is keyed by the step index; the table needs a routed kernel): the k-step kernel, or
+    // the issued launches when the AoS head is written (fpv_step_n writes none)
+    if (b->reset_pose || (h->K.flags & FPV_FLAG_RESET_JITTER))
+        return b->obs_aos ? fpv_rollout(h, b, k, action_stride, out_stride, stream) : fpv_step_n(h, b, k, action_stride, out_stride, stream);
     const DeviceGuard dev(h->device);
     if (dev.rc != FPV_OK) return dev.rc;
-    const FpvBufD d0 = to_device_view(b, h->K.contact_reach);
+    const FpvBufD d0 = to_device_view(h, b);
     // SHAPE of the graph: everything that selects kernels, grids and non-pointer arguments
     const KernelChoice c0 = choose_kernel(h, d0);
     std::string shape(reinterpret_cast<const char*>(&h->K), sizeof(h->K));

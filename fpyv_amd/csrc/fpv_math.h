@@ -869,6 +869,62 @@ FPV_HD void fpv_drone_reset_lane(const FpvK& K, FpvDroneState& s)
     s.thrust = 0.0f;
 }
 
+// ------------------------------------------------------------------------------------------------
+// Reset sources (FPV_FLAG_RESET_JITTER, fpv_buffers_t.reset_pose; include/fpv_abi.h): a reset lane starts from its base
+// pose - its row of the reset-pose table or the handle's init_* - plus a uniform box jitter:
+//   p += U[pos], v += U[vel], q <- q (x) quat_from_rpy_deg(U[ypr])
+// Each sample is fmaf(span, u, lo) with u = (w >> 8) * 2^-24 of one Philox4x32-7 word: key = reset_seed, counter =
+// (gid lo, gid hi ^ (block << 28) ^ (explicit << 31), step lo, step hi), block 0 / 1 / 2 = position / velocity / angles,
+// words 0..2 = the three components.  Keyed by global drone id and step index only: the same draw on every shard,
+// partition and kernel.  fpv_reset_pose_sample (host) runs this function, so the kernels can be checked against it.
+// ------------------------------------------------------------------------------------------------
+#define FPV_MATH_FLAG_RESET_JITTER 16u   // = FPV_FLAG_RESET_JITTER
+
+struct FpvResetJitter {      // narrowed on the host (fpv_derive_reset_jitter): lo and hi - lo of the nine boxes
+    float lo[9], span[9];    // p xyz, v xyz, roll pitch yaw (deg)
+    uint32_t seed_lo, seed_hi;
+};
+
+// a (x) b, Hamilton product (w, x, y, z)
+FPV_HD FpvQuat fpv_quat_mul(FpvQuat a, FpvQuat b)
+{
+    FpvQuat r;
+    r.w = fmaf(a.w, b.w, fmaf(-a.x, b.x, fmaf(-a.y, b.y, -(a.z * b.z))));
+    r.x = fmaf(a.w, b.x, fmaf(a.x, b.w, fmaf(a.y, b.z, -(a.z * b.y))));
+    r.y = fmaf(a.w, b.y, fmaf(-a.x, b.z, fmaf(a.y, b.w, a.z * b.x)));
+    r.z = fmaf(a.w, b.z, fmaf(a.x, b.y, fmaf(-a.y, b.x, a.z * b.w)));
+    return r;
+}
+
+// one block of the jitter on the pose p3 v3 q4 (wxyz), in place: b = 0 position, 1 velocity, 2 roll/pitch/yaw (body frame)
+FPV_HD void fpv_reset_jitter_block(const float lo[3], const float span[3], uint32_t seed_lo, uint32_t seed_hi, uint64_t gid,
+                                   uint64_t step, uint32_t explicit_reset, uint32_t b, float pose[10])
+{
+    uint32_t w[4];
+    fpv_philox4x32<FPV_NOISE_PHILOX_ROUNDS>((uint32_t)gid, (uint32_t)(gid >> 32) ^ (b << 28) ^ (explicit_reset << 31),
+                                            (uint32_t)step, (uint32_t)(step >> 32), seed_lo, seed_hi, w);
+    float r[3];
+#pragma unroll
+    for (int c = 0; c < 3; ++c) r[c] = fmaf(span[c], (float)(w[c] >> 8) * 0x1p-24f, lo[c]);
+    if (b < 2) {
+#pragma unroll
+        for (int c = 0; c < 3; ++c) pose[3 * b + c] += r[c];
+    } else {
+        FpvQuat q;
+        q.w = pose[6]; q.x = pose[7]; q.y = pose[8]; q.z = pose[9];
+        q = fpv_quat_mul(q, fpv_quat_from_rpy_deg(r[0], r[1], r[2]));
+        pose[6] = q.w; pose[7] = q.x; pose[8] = q.y; pose[9] = q.z;
+    }
+}
+
+// jitters the base pose of one reset lane in place: pose = p3 v3 q4 (wxyz)
+FPV_HD void fpv_reset_jitter(const FpvResetJitter& J, uint64_t gid, uint64_t step, uint32_t explicit_reset, float pose[10])
+{
+#pragma unroll
+    for (uint32_t b = 0; b < 3; ++b)
+        fpv_reset_jitter_block(J.lo + 3 * b, J.span + 3 * b, J.seed_lo, J.seed_hi, gid, step, explicit_reset, b, pose);
+}
+
 // sin and cos of an UNBOUNDED angle in float64, the same instruction sequence on the host and on
 // gfx950 (explicit fma, no library call): three-part Cody-Waite reduction by pi/2 (each part has
 // 33 significant bits, so k * part is exact for |k| < 2^20, i.e. |x| < 1.6e6 rad) and the Taylor

@@ -48,7 +48,7 @@ class _Batch:
                  track_episodes: bool = False, with_accel: bool = False, with_done_bits: bool = False,
                  fp16_state: bool = False, rounding_seed: int = 0, with_obs_aos: bool = False,
                  stick_noise: bool = False, noise_seed: int = 0, drone_id_offset: int = 0,
-                 with_action_out: bool = False, kahan_position: bool = False):
+                 with_action_out: bool = False, kahan_position: bool = False, per_drone_reset_pose: bool = False):
         if num_envs <= 0:
             raise ValueError("num_envs must be positive")
         self.params = params
@@ -103,6 +103,15 @@ class _Batch:
         self.action_out = torch.zeros((self.n, 4), **f32) if with_action_out else None
         # optional row-major [num_envs, 16] observation written by the kernel through an LDS transpose
         self.obs_aos = (torch.zeros((self.n, _lib.FPV_OBS_AOS_DIM), **f32) if with_obs_aos else None)
+        # per-drone reset poses (fpv_buffers_t.reset_pose): [10, ld] p3 v3 q4, the base pose of every reset of a drone - what a
+        # reset(position=, velocity=, ypr=) gave it, so that the in-kernel auto-reset returns it to ITS start; initialised to the
+        # init_* the handle narrowed (until a per-drone reset is made, every reset is the one it was without the table)
+        self.reset_pose = None
+        if per_drone_reset_pose:
+            if self.mode != MODE_DRONE:
+                raise ValueError("per_drone_reset_pose is a drone-mode option (the Racer resets to its zero state)")
+            self.reset_pose = torch.empty((_lib.RESET_POSE_ROWS, self.ld), **f32)
+            self.reset_pose.copy_(torch.from_numpy(self._init_pose()).view(-1, 1).expand(_lib.RESET_POSE_ROWS, self.ld))
         self._bcast_action = None
         self._objects = None            # the bound fpv_objects_t (None = no collision world bound)
         self._object_rows = None
@@ -130,6 +139,15 @@ class _Batch:
         b.obs_aos = ptr(self.obs_aos)
         b.noise_state, b.action_out = ptr(self.noise_state), ptr(self.action_out)
         b.pos_comp = ptr(self.pos_comp)
+        b.reset_pose = ptr(self.reset_pose)
+
+    def _init_pose(self) -> np.ndarray:
+        """init_position / init_velocity / init_quat as fpv_create narrows them (fpv_derive.h: the quaternion divided by its
+        float64 norm, summed in the same order, then rounded to fp32): [10] float32"""
+        c = self._cparams
+        q = [float(c.init_quat[k]) for k in range(4)]
+        qn = (q[0] * q[0] + q[1] * q[1] + q[2] * q[2] + q[3] * q[3]) ** 0.5
+        return np.array(list(c.init_position) + list(c.init_velocity) + [x / qn for x in q], dtype=np.float32)
 
     def rows_f32(self, r0: int, r1: int) -> torch.Tensor:
         """[num_envs, r1-r0] fp32 values of state rows r0..r1-1 (fpv_abi.h row numbering), whatever the
@@ -274,8 +292,8 @@ class _Batch:
 
     # -- checkpoint / resume (the reference has none; state is just tensors here) ------------------
     _CKPT_TENSORS = ("state", "state_h", "reward", "done", "ep_return", "ep_length", "last_return",
-                     "last_length", "noise_state", "pos_comp")
-    _CKPT_ROW_TENSORS = ("state", "noise_state", "pos_comp")        # [rows, ld]: stored as their logical columns [rows, num_envs]
+                     "last_length", "noise_state", "pos_comp", "reset_pose")
+    _CKPT_ROW_TENSORS = ("state", "noise_state", "pos_comp", "reset_pose")        # [rows, ld]: stored as their logical columns [rows, num_envs]
 
     def _state_h_views(self, t: Optional[torch.Tensor] = None, ld: Optional[int] = None):
         """(pair rows [5, ld, 2], thrust row [ld]) int16 views of an fp16 storage tensor laid out with row stride `ld`"""
@@ -583,6 +601,7 @@ class _Partition:
         b.reward, b.done = off(pb.reward, 4), off(pb.done, 1)
         b.done_bits = (pb.done_bits + (lo // 64) * 8) if pb.done_bits else None
         b.accel, b.pos_comp, b.noise_state = off(pb.accel, 4), off(pb.pos_comp, 4), off(pb.noise_state, 4)
+        b.reset_pose = off(pb.reset_pose, 4)
         b.ep_return, b.ep_length = off(pb.ep_return, 4), off(pb.ep_length, 4)
         b.last_return, b.last_length = off(pb.last_return, 4), off(pb.last_length, 4)
         b.action_out, b.obs_aos = off(pb.action_out, 4, 4), off(pb.obs_aos, 4, _lib.FPV_OBS_AOS_DIM)
@@ -767,7 +786,9 @@ class DroneBatch(_Batch):
     def reset(self, position=None, velocity=None, ypr=None, mask=None) -> None:
         """Drone.reset: `ypr` is consumed as (roll, pitch, yaw) in degrees, like the reference
         (components.py:150-154).  Arguments broadcast from [3] or are per drone [num_envs, 3];
-        None uses params.init_*."""
+        None uses params.init_* - or, with per_drone_reset_pose=True, the drone's own start, which the given arguments
+        replace: the in-kernel auto-reset then returns every drone to its start.  With a reset jitter
+        (DroneParams.reset_*_range) the pose gets its random offset on top."""
         self._reset_raw(mask=mask, position=position, velocity=velocity, ypr=ypr)
         if self._force_multiplier_pid is not None:
             self._force_multiplier_pid.reset(mask)                  # components.py:166
@@ -988,12 +1009,23 @@ class FpvVecEnv:
             if cur != P.stream:
                 P.stream.wait_stream(cur)
 
-    def reset(self, mask=None) -> torch.Tensor:
+    def reset(self, mask=None, *, position=None, velocity=None, ypr=None) -> torch.Tensor:
+        """Reset the drones of `mask` (None = all).  `position` / `velocity` / `ypr` (drone mode; [3] or [num_envs, 3], ypr as
+        (roll, pitch, yaw) degrees) are DroneBatch.reset's per-drone starts; with per_drone_reset_pose=True they survive the
+        in-kernel auto-reset."""
+        kw = {}
+        if position is not None or velocity is not None or ypr is not None:
+            if not isinstance(self.batch, DroneBatch):
+                raise ValueError("position / velocity / ypr are drone-mode reset arguments")
+            kw = dict(position=position, velocity=velocity, ypr=ypr)
         if not self._parts:
-            self.batch.reset(mask=mask)
+            self.batch.reset(mask=mask, **kw)
             return self.obs
         cur = self._caller_waits_for_partitions()      # steps still in flight on the partitions' streams finish first
-        self.batch.reset(mask=mask)                    # (the step counters run on, as the unpartitioned batch's does across a reset)
+        if self.batch._cparams.flags & _lib.FPV_FLAG_RESET_JITTER:
+            # the jitter of an explicit reset is keyed by the step counter: the partitions', which stepped this population
+            self.batch.set_step_counter(min(P.steps_launched for P in self._parts))
+        self.batch.reset(mask=mask, **kw)              # (the step counters run on, as the unpartitioned batch's does across a reset)
         self._partitions_wait_for(cur)
         return self.obs
 

@@ -146,6 +146,13 @@ class DroneParams:
     # ordered object_list for the collision pass (components.py:198-214): tuples
     # (type, x, y, z, radius, height) with type 0 = Ground, 1 = Cylinder, 2 = Target sphere; max 8
     objects: tuple = ()
+    # randomised reset poses (FPV_FLAG_RESET_JITTER): each None or [[lo x, lo y, lo z], [hi x, hi y, hi z]] - a uniform box added
+    # to the base pose of every reset (position m, velocity m/s, roll/pitch/yaw deg applied in the body frame); setting any of
+    # them turns the jitter on (a box left at None is [0, 0]); `reset_seed` keys the draws
+    reset_position_range: Optional[Any] = None
+    reset_velocity_range: Optional[Any] = None
+    reset_ypr_range_deg: Optional[Any] = None
+    reset_seed: int = 0
 
     @property
     def init_quat(self) -> np.ndarray:

@@ -45,7 +45,10 @@ extern "C" {
  *    gfx950 with 256 compute units and a 4 MiB L2 per XCD (e.g. a CPX compute partition) gets the plain order and the
  *    conservative stride - same results.  Every single-step kernel rotates (drone fp32 / fp16 state / AoS head / Racer), as ABI 7
  *    already did; its comment said "fp32 drone" only.  fpv_encoding_id added (what a checkpoint's fp16 words / noise stream mean). */
-#define FPV_ABI_VERSION 8
+/* 9: reset sources for drone mode - a per-lane reset-pose table (fpv_buffers_t.reset_pose) and a seeded uniform jitter of the
+ *    reset pose (FPV_FLAG_RESET_JITTER, fpv_params_t.reset_*_range / reset_seed, appended); fpv_reset_pose_sample added.
+ *    Nothing changes for a handle that configures neither (state layout, streams and checkpoints of ABI 5-8 included). */
+#define FPV_ABI_VERSION 9
 
 enum {
     FPV_OK = 0,
@@ -92,6 +95,8 @@ enum {
                                    per drone and channel (the profile of tests/noise_smooth_test.py:6-12, Philox4x32-7 + a table-driven inverse normal CDF,
                                    keyed by seed / global drone id / step) and ADDS gain * noise to the action
                                    (clipped to [-1,1]); fpv_buffers_t.action may then be NULL (pure noise sticks) */
+    FPV_FLAG_RESET_JITTER = 16u,/* drone mode: every reset (fpv_reset and the in-kernel auto-reset) adds a uniform jitter to its base
+                                   pose (fpv_params_t.reset_*; "Reset sources" below) */
     FPV_FLAG_FP16_STATE = 4u    /* drone mode only: v, q, prev_rates, prev_thrust stored as eleven 16-bit words per drone in
                                    fpv_buffers_t.state_h; fpv_buffers_t.state holds only the 3 position rows in
                                    fp32; arithmetic stays fp32 (BASELINE config 4) */
@@ -158,6 +163,13 @@ typedef struct fpv_params {
     double pid_min_output;            /*                            0.3 */
     double pid_max_output;            /*                            1 */
     double pid_derivative_transition_rate;   /*                     0.5 */
+    /* FPV_FLAG_RESET_JITTER (ABI 9): uniform boxes [lo row, hi row] added to the base pose of every reset (position m,
+     * velocity m/s, roll/pitch/yaw deg applied in the body frame); finite with lo <= hi (else FPV_EPARAM), narrowed to fp32 as
+     * lo and span = hi - lo (computed in double).  Unused without the flag. */
+    double reset_pos_range[2][3];
+    double reset_vel_range[2][3];
+    double reset_ypr_range_deg[2][3];
+    uint64_t reset_seed;              /* Philox key of the jitter */
 } fpv_params_t;
 
 /* Analytic collision objects = the reference's object_list (components.py:198-214) in list order.
@@ -219,7 +231,34 @@ typedef struct fpv_buffers {
                                 state_h + 2 * FPV_HALF_PAIR_ROWS * ld - i.e. for a handle that steps a column range [lo, hi) of a
                                 larger batch (state_h moved by 2 * lo halves, this pointer = the batch's thrust row + lo halves;
                                 4-byte aligned: lo even); NULL = the row follows the pair rows */
+    float* reset_pose;       /* ABI 9, drone mode: [10][ld] per-lane reset pose (rows p3 v3 q4 wxyz, the state's row order) or NULL:
+                                the base pose of every reset of the lane ("Reset sources" below); 16-byte aligned.  Read only by
+                                lanes that reset, written by fpv_reset when it is given position / velocity / ypr_deg */
 } fpv_buffers_t;
+
+/* Reset sources (ABI 9, drone mode: fp32 and fp16 state, every step entry point).  Every reset of a lane - fpv_reset or the
+ * in-kernel reset of FPV_FLAG_AUTO_RESET - produces
+ *   base  = the lane's row of fpv_buffers_t.reset_pose when it is given, else fpv_reset's arguments / init_* (as before)
+ *   p = base.p + U[pos], v = base.v + U[vel], q = base.q (x) quat_from_rpy_deg(U[ypr])    (FPV_FLAG_RESET_JITTER only)
+ *   prev_rates = 0, prev_thrust = 0; episode counters, noise state and Kahan rows zeroed as before.
+ * fpv_reset with a table: position / velocity / ypr_deg, where given, replace the corresponding rows of the table for the
+ * masked lanes (the quaternion stored is that of ypr_deg), and the lane then starts from its table row - so a later auto-reset
+ * returns each drone to its own start.  A table starts as whatever the caller wrote (fpyv_amd: init_*).
+ * Jitter sample = fmaf(span, u, lo), u = (w >> 8) * 2^-24 of a Philox4x32-7 word w: key = reset_seed; counter =
+ * (gid lo, gid hi ^ (b << 28) ^ (e << 31), t lo, t hi) with b = 0 position / 1 velocity / 2 angles (words 0..2 = components),
+ * gid = drone_id_offset + lane (the stick noise's global id), e = 1 for fpv_reset and 0 in-kernel, t = the step index of the
+ * step in which the lane reported done (fpv_reset: the handle's step counter at the call).  The draw depends on (seed, gid, t)
+ * only: the same for every shard, partition and single-step / k-step choice.  fpv_reset_pose_sample is the same arithmetic on
+ * the host.
+ * Routing: a handle with a reset source runs its single-step launches (fpv_step, fpv_rollout) on the k-step kernel with k = 1
+ * (bit-identical to the single-step kernel, which stays free of the reset-source code); with obs_aos they keep the AoS kernel;
+ * fpv_rollout_graph serves them like FPV_FLAG_STICK_NOISE handles (fpv_step_n; fpv_rollout with obs_aos).
+ * Refused (FPV_EINVAL): either source on a Racer handle; either source together with rotation_override. */
+/* out = the pose a reset of drone `global_id` in step `step` gives a lane whose base pose is `base` (p3 v3 q4), explicit_reset = 1
+ * for fpv_reset, 0 for the in-kernel reset; out = base bit for bit without FPV_FLAG_RESET_JITTER.  Host arithmetic only (no
+ * device needed), the kernels' own function; the parameters are checked as fpv_create checks them. */
+int fpv_reset_pose_sample(const fpv_params_t* params, uint64_t global_id, uint64_t step, int explicit_reset,
+                          const float base[10], float out[10]);
 
 typedef struct fpv_env* fpv_handle_t;
 
