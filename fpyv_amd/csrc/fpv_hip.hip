@@ -1119,6 +1119,21 @@ int hip_fail(hipError_t e, const char* what)
                 std::string(what) + ": " + hipGetErrorString(e));
 }
 
+// workgroups of `block` threads, one thread per item, for n items
+inline dim3 blocks_for(int64_t n, int block) { return dim3((unsigned)((n + block - 1) / block)); }
+
+template <class T> struct exactly { typedef T type; };      // a parameter type that takes no part in template deduction
+
+// One kernel launch and its check: FPV_OK, or the launch's error under `what`.  The arguments take the kernel's own parameter
+// types (P is deduced from the kernel alone), so every argument converts as it would in a direct call.
+template <class... P>
+int launch(const char* what, void (*kernel)(P...), dim3 grid, dim3 block, hipStream_t s, const typename exactly<P>::type&... args)
+{
+    hipLaunchKernelGGL(kernel, grid, block, 0, s, args...);
+    const hipError_t e = hipGetLastError();
+    return e == hipSuccess ? FPV_OK : hip_fail(e, what);
+}
+
 }  // namespace
 
 struct fpv_env {
@@ -1270,51 +1285,35 @@ struct DeviceGuard {
     DeviceGuard& operator=(const DeviceGuard&) = delete;
 };
 
-// ---- kernel selection: every step kernel has the signature FPV_STEP_PARAMS ------------------------------
+// ---- kernel selection: every step kernel has the signature FPV_STEP_PARAMS, every k-step kernel (fpv_step_n) one FpvRollArgs ----
 typedef void (*StepKernel)(float*, const int64_t, const float4*, const int64_t, uint16_t*, const int64_t, const FpvK, const FpvBufD);
 typedef void (*RollKernel)(const FpvRollArgs);
-// func = a single-step kernel (FPV_STEP_PARAMS), or null and roll = a k-step kernel launched with k = 1 (reset sources, below)
-struct KernelChoice { StepKernel func; unsigned grid, block; RollKernel roll; };
-// blocks of one single-step launch: n's, in whole rounds of the eight XCDs (FPV_STEP_INDEX computes the same number from n)
+// blocks of one single-step launch: n's, in whole rounds of the eight XCDs - every single-step kernel (drone, fp16 state, AoS head,
+// Racer) reads n and the start block from one argument, and FPV_STEP_INDEX computes the same number from n
 inline int64_t step_grid(int64_t n) { return (n + 8 * kStepBlock - 1) / (8 * kStepBlock) * 8; }
 
-StepKernel drone_kernel(bool noise, bool obj, bool kahan)
-{
-    // optional features of the step kernel are independent template switches (in-kernel stick noise x object_list
-    // collisions x Kahan rows), each combination its own instantiation, so the plain kernel keeps its register budget
-    switch ((noise ? 4 : 0) | (obj ? 2 : 0) | (kahan ? 1 : 0)) {
-        case 0: return fpv_drone_step_kernel<false, false, false>;
-        case 1: return fpv_drone_step_kernel<false, false, true>;
-        case 2: return fpv_drone_step_kernel<false, true, false>;
-        case 3: return fpv_drone_step_kernel<false, true, true>;
-        case 4: return fpv_drone_step_kernel<true, false, false>;
-        case 5: return fpv_drone_step_kernel<true, false, true>;
-        case 6: return fpv_drone_step_kernel<true, true, false>;
-        default: return fpv_drone_step_kernel<true, true, true>;
-    }
-}
-
-StepKernel racer_kernel(bool wide, bool pidv)
-{
-    return wide ? (pidv ? fpv_racer_step_kernel<true, true> : fpv_racer_step_kernel<true, false>)
-                : (pidv ? fpv_racer_step_kernel<false, true> : fpv_racer_step_kernel<false, false>);
-}
-
-// ---- k-step kernels (fpv_step_n): one FpvRollArgs parameter ----
-
-RollKernel drone_rollout_kernel(bool noise, bool obj, bool kahan, bool sq)
-{
-    switch ((noise ? 4 : 0) | (obj ? 2 : 0) | (kahan ? 1 : 0)) {
-        case 0: return sq ? fpv_drone_rollout_kernel<false, false, false, true> : fpv_drone_rollout_kernel<false, false, false>;
-        case 1: return sq ? fpv_drone_rollout_kernel<false, false, true, true> : fpv_drone_rollout_kernel<false, false, true>;
-        case 2: return fpv_drone_rollout_kernel<false, true, false>;
-        case 3: return fpv_drone_rollout_kernel<false, true, true>;
-        case 4: return sq ? fpv_drone_rollout_kernel<true, false, false, true> : fpv_drone_rollout_kernel<true, false, false>;
-        case 5: return sq ? fpv_drone_rollout_kernel<true, false, true, true> : fpv_drone_rollout_kernel<true, false, true>;
-        case 6: return fpv_drone_rollout_kernel<true, true, false>;
-        default: return fpv_drone_rollout_kernel<true, true, true>;
-    }
-}
+// Optional features of the drone kernels are independent template switches (in-kernel stick noise x object_list collisions x
+// Kahan rows), each combination its own instantiation, so the plain kernel keeps its register budget.  Tables [noise][obj][kahan];
+// the SQ k-step bodies exist without the object list only: [noise][kahan].  Racer: [wide][pid variant].
+const StepKernel kDroneStep[2][2][2] = {
+    {{fpv_drone_step_kernel<false, false, false>, fpv_drone_step_kernel<false, false, true>},
+     {fpv_drone_step_kernel<false, true, false>, fpv_drone_step_kernel<false, true, true>}},
+    {{fpv_drone_step_kernel<true, false, false>, fpv_drone_step_kernel<true, false, true>},
+     {fpv_drone_step_kernel<true, true, false>, fpv_drone_step_kernel<true, true, true>}}};
+// guidance override: the plain or the object-list kernel (check_buffers), [obj]
+const StepKernel kDroneStepOverride[2] = {fpv_drone_step_kernel<false, false, false, true>, fpv_drone_step_kernel<false, true, false, true>};
+const RollKernel kDroneRoll[2][2][2] = {
+    {{fpv_drone_rollout_kernel<false, false, false>, fpv_drone_rollout_kernel<false, false, true>},
+     {fpv_drone_rollout_kernel<false, true, false>, fpv_drone_rollout_kernel<false, true, true>}},
+    {{fpv_drone_rollout_kernel<true, false, false>, fpv_drone_rollout_kernel<true, false, true>},
+     {fpv_drone_rollout_kernel<true, true, false>, fpv_drone_rollout_kernel<true, true, true>}}};
+const RollKernel kDroneRollSq[2][2] = {
+    {fpv_drone_rollout_kernel<false, false, false, true>, fpv_drone_rollout_kernel<false, false, true, true>},
+    {fpv_drone_rollout_kernel<true, false, false, true>, fpv_drone_rollout_kernel<true, false, true, true>}};
+const StepKernel kRacerStep[2][2] = {{fpv_racer_step_kernel<false, false>, fpv_racer_step_kernel<false, true>},
+                                     {fpv_racer_step_kernel<true, false>, fpv_racer_step_kernel<true, true>}};
+const RollKernel kRacerRoll[2][2] = {{fpv_racer_rollout_kernel<false, false>, fpv_racer_rollout_kernel<false, true>},
+                                     {fpv_racer_rollout_kernel<true, false>, fpv_racer_rollout_kernel<true, true>}};
 
 // Reset sources (fpv_abi.h: the reset-pose table, FPV_FLAG_RESET_JITTER) live in the rare reset branch of the kernels that are
 // NOT on the headline path: the non-SQ k-step kernels, the fp16 k-step kernel, the AoS-head kernel and the reset kernel.  The
@@ -1335,44 +1334,35 @@ bool has_reset_source(const fpv_env* h, const FpvBufD& d)
 
 RollKernel choose_rollout_kernel(const fpv_env* h, const FpvBufD& d)
 {
-    if (h->mode != FPV_MODE_DRONE) {
-        const bool wide = h->K.r_wide != 0, pidv = h->K.r_pid_variant != 0;
-        return wide ? (pidv ? fpv_racer_rollout_kernel<true, true> : fpv_racer_rollout_kernel<true, false>)
-                    : (pidv ? fpv_racer_rollout_kernel<false, true> : fpv_racer_rollout_kernel<false, false>);
-    }
+    if (h->mode != FPV_MODE_DRONE) return kRacerRoll[h->K.r_wide != 0][h->K.r_pid_variant != 0];
     if (h->K.flags & FPV_FLAG_FP16_STATE) return fpv_drone_rollout_h_kernel;
     const bool noise = (h->K.flags & FPV_FLAG_STICK_NOISE) != 0, obj = d.objs.count > 0, kahan = d.pos_comp != nullptr;
     const bool sq = !obj && h->K.motor_square && !(h->K.flags & FPV_FLAG_GROUND)      // X frame, no ground springs
                     && !has_reset_source(h, d);                                          // (the SQ bodies carry no reset source)
-    return drone_rollout_kernel(noise, obj, kahan, sq);
+    return sq ? kDroneRollSq[noise][kahan] : kDroneRoll[noise][obj][kahan];
 }
 
-KernelChoice choose_kernel(const fpv_env* h, const FpvBufD& d)
+// the single-step kernel (FPV_STEP_PARAMS) of a launch, or null: the launch is one step of the k-step kernel (reset sources, above)
+StepKernel choose_kernel(const fpv_env* h, const FpvBufD& d)
 {
-    KernelChoice c;
-    c.block = (unsigned)kStepBlock;
-    c.roll = nullptr;
-    if (has_reset_source(h, d) && !d.obs_aos) {          // routed around the pinned single-step kernels (see has_reset_source)
-        c.func = nullptr;
-        c.roll = choose_rollout_kernel(h, d);
-        c.grid = (unsigned)((h->n + kStepBlock - 1) / kStepBlock);
-        return c;
-    }
-    if (h->mode != FPV_MODE_DRONE) {
-        c.func = racer_kernel(h->K.r_wide != 0, h->K.r_pid_variant != 0);
-    } else if (h->K.flags & FPV_FLAG_FP16_STATE) {
-        c.func = fpv_drone_step_h_kernel;
-    } else if (d.obs_aos) {
-        c.func = fpv_drone_step_aos_kernel;
-    } else {
-        const bool noise = (h->K.flags & FPV_FLAG_STICK_NOISE) != 0, obj = d.objs.count > 0, kahan = d.pos_comp != nullptr;
-        if (d.rot_over)                     // guidance override: plain or object-list kernel (check_buffers)
-            c.func = obj ? fpv_drone_step_kernel<false, true, false, true> : fpv_drone_step_kernel<false, false, false, true>;
-        else
-            c.func = drone_kernel(noise, obj, kahan);
-    }
-    c.grid = (unsigned)step_grid(h->n);      // every single-step kernel - drone, fp16 state, AoS head, Racer - reads n and the start block from one argument (FPV_STEP_INDEX)
-    return c;
+    if (has_reset_source(h, d) && !d.obs_aos) return nullptr;      // routed around the pinned single-step kernels (see has_reset_source)
+    if (h->mode != FPV_MODE_DRONE) return kRacerStep[h->K.r_wide != 0][h->K.r_pid_variant != 0];
+    if (h->K.flags & FPV_FLAG_FP16_STATE) return fpv_drone_step_h_kernel;
+    if (d.obs_aos) return fpv_drone_step_aos_kernel;
+    const bool noise = (h->K.flags & FPV_FLAG_STICK_NOISE) != 0, obj = d.objs.count > 0, kahan = d.pos_comp != nullptr;
+    return d.rot_over ? kDroneStepOverride[obj] : kDroneStep[noise][obj][kahan];
+}
+
+// one launch of the k-step kernel over the handle's drones, R.k steps from the step index d.step; an accepted launch advances
+// the handle's step index by R.k
+int launch_roll(fpv_env* h, const FpvBufD& d, const FpvRoll& R, hipStream_t s, const char* what)
+{
+    FpvRollArgs args;
+    memset(&args, 0, sizeof(args));
+    args.K = h->K; args.B = d; args.n = h->n; args.R = R;
+    const int rc = launch(what, choose_rollout_kernel(h, d), blocks_for(h->n, kStepBlock), dim3(kStepBlock), s, args);
+    if (rc == FPV_OK) h->launches += (uint64_t)R.k;
+    return rc;
 }
 
 int64_t rotation_blocks(const fpv_env* h, const FpvBufD* d);      // below, with the cache sizes
@@ -1381,25 +1371,15 @@ int launch_step(fpv_env* h, const FpvBufD& d_in, hipStream_t s)
 {
     FpvBufD d = d_in;
     d.step = h->launches;
-    const KernelChoice c = choose_kernel(h, d);
-    if (c.roll) {
-        // one step of the k-step kernel: reward / done / done_bits / episode sums leave after it, as after a single step
-        FpvRollArgs args;
-        memset(&args, 0, sizeof(args));
-        args.K = h->K; args.B = d; args.n = h->n;
-        args.R.k = 1; args.R.bits_stride = 0;
-        hipLaunchKernelGGL(c.roll, dim3(c.grid), dim3(c.block), 0, s, args);
-        const hipError_t e = hipGetLastError();
-        if (e != hipSuccess) return hip_fail(e, "step kernel launch");
-        ++h->launches;
-        return FPV_OK;
-    }
-    const int64_t nblk = (int64_t)c.grid;
+    const StepKernel f = choose_kernel(h, d);
+    // one step of the k-step kernel: reward / done / done_bits / episode sums leave after it, as after a single step
+    if (!f) return launch_roll(h, d, FpvRoll{1, 0, 0, 0, 0}, s, "step kernel launch");
+    const int64_t nblk = step_grid(h->n);
     h->rot_blocks = rotation_blocks(h, &d);
     const int64_t start = h->rot_blocks > 0 ? h->start_block % nblk : 0;
-    hipLaunchKernelGGL(c.func, dim3(c.grid), dim3(c.block), 0, s, d.state, d.ld, d.action, d.action_ld, d.state_h, h->n | (start << 32), h->K, d);
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return hip_fail(e, "step kernel launch");
+    const int rc = launch("step kernel launch", f, dim3((unsigned)nblk), dim3(kStepBlock), s, d.state, d.ld, d.action, d.action_ld, d.state_h,
+                          h->n | (start << 32), h->K, d);
+    if (rc != FPV_OK) return rc;
     ++h->launches;                     // a refused launch leaves the step index where it was
     if (h->rot_blocks > 0) h->start_block = (start + nblk - h->rot_blocks % nblk) % nblk;
     return FPV_OK;
@@ -1454,19 +1434,35 @@ int device_cache_model(int device, fpv_cache_model_t* out)
 {
     static std::mutex mu;
     static std::vector<std::pair<int, fpv_cache_model_t>> known;
+    const auto cached = [&] {                   // under mu
+        for (const auto& k : known)
+            if (k.first == device) { *out = k.second; return true; }
+        return false;
+    };
     {
         const std::lock_guard<std::mutex> lock(mu);
-        for (const auto& k : known)
-            if (k.first == device) { *out = k.second; return FPV_OK; }
+        if (cached()) return FPV_OK;
     }
     hipDeviceProp_t prop;
     const hipError_t e = hipGetDeviceProperties(&prop, device);
     if (e != hipSuccess) return hip_fail(e, "hipGetDeviceProperties");
     check_cache_model(prop.gcnArchName, prop.multiProcessorCount, (int64_t)prop.l2CacheSize, out);
     const std::lock_guard<std::mutex> lock(mu);
-    known.emplace_back(device, *out);
+    if (!cached()) known.emplace_back(device, *out);      // another thread may have asked for the same device meanwhile
     return FPV_OK;
 }
+
+// Bytes of one drone's state in a layout (`K` = a handle's constants, or null for the mode's base layout): 14 fp32 rows; fp16
+// state: 3 fp32 rows, the half-pair rows and the thrust half; Racer: 20 base rows (+6 (hi, lo) rows as written, +3 components.PID)
+int state_bytes(int mode, const FpvK* K)
+{
+    if (mode == FPV_MODE_RACER) return 4 * (20 + (K && K->r_wide ? 6 : 0) + (K && K->r_pid_variant ? 3 : 0));
+    if (K && (K->flags & FPV_FLAG_FP16_STATE)) return 3 * 4 + FPV_HALF_PAIR_ROWS * 4 + 2;
+    return 4 * FPV_DRONE_ROWS;
+}
+
+// what one step moves per drone (fpv_algorithmic_bytes): state read + write, action read, reward + done write
+int algorithmic_bytes(int mode, const FpvK* K) { return state_bytes(mode, K) * 2 + 16 + 4 + 1; }
 
 // Bytes per drone that one launch WRITES and that compete for a cache between two visits of a drone (reads of rows that are
 // written back are the same lines).  The plain kernel: 14 rows + reward + done = 61 B, and 4096 blocks of 128 drones x 61 B are the
@@ -1476,10 +1472,7 @@ int device_cache_model(int device, fpv_cache_model_t* out)
 // or null for an estimate from the handle alone (fpv_get_rotation before the first launch).
 int64_t written_bytes_per_drone(const fpv_env* h, const FpvBufD* d)
 {
-    int64_t b;
-    if (h->mode == FPV_MODE_RACER) b = 4 * (20 + (h->K.r_wide ? 6 : 0) + (h->K.r_pid_variant ? 3 : 0));
-    else if (h->K.flags & FPV_FLAG_FP16_STATE) b = 3 * 4 + FPV_HALF_PAIR_ROWS * 4 + 2;
-    else b = 4 * FPV_DRONE_ROWS;
+    int64_t b = state_bytes(h->mode, &h->K);
     if (h->K.flags & FPV_FLAG_STICK_NOISE) b += 16;            // the four EMA rows
     if (!d) return b + 5;
     if (d->reward) b += 4;
@@ -1543,15 +1536,30 @@ double l2_set_overflow(int64_t stride_bytes, int64_t blocks)
     return worst;
 }
 
-// node t of a replayed graph: the same rotation, counted from the first node (a replay begins where the previous one began: one
-// launch in k starts on cold rows)
-int64_t graph_n_start(const fpv_env* h, const KernelChoice& c, const FpvBufD& d, int t)
-{
-    const int64_t nblk = (int64_t)c.grid;
-    const int64_t rot = rotation_blocks(h, &d);
-    const int64_t start = rot > 0 ? (int64_t)(((uint64_t)t * (uint64_t)(nblk - rot % nblk)) % (uint64_t)nblk) : 0;
-    return h->n | (start << 32);
-}
+// The kernel node of step t of a graph, filled in place: np.kernelParams points at this object's own d, n_start and K, which
+// hipGraphAddKernelNode / hipGraphExecKernelNodeSetParams copy - so it is used where it is built and never copied.  Node t has
+// launch_step's rotation, counted from the first node (a replay begins where the previous one began: one launch in k starts on
+// cold rows).
+struct GraphNode {
+    FpvBufD d;
+    FpvK K;
+    int64_t n_start;
+    void* args[8];
+    hipKernelNodeParams np;
+    GraphNode(const fpv_env* h, const FpvBufD& dt, int t)
+        : d(dt), K(h->K), args{&d.state, &d.ld, &d.action, &d.action_ld, &d.state_h, &n_start, &K, &d}
+    {
+        const int64_t nblk = step_grid(h->n), rot = rotation_blocks(h, &d);
+        const int64_t start = rot > 0 ? (int64_t)(((uint64_t)t * (uint64_t)(nblk - rot % nblk)) % (uint64_t)nblk) : 0;
+        n_start = h->n | (start << 32);
+        memset(&np, 0, sizeof(np));
+        np.func = reinterpret_cast<void*>(choose_kernel(h, d));
+        np.gridDim = dim3((unsigned)nblk); np.blockDim = dim3(kStepBlock);
+        np.kernelParams = args;
+    }
+    GraphNode(const GraphNode&) = delete;
+    GraphNode& operator=(const GraphNode&) = delete;
+};
 
 // The row stride that needs no model of the caches: n rounded up to 64 floats and kept at least 1 KiB past a multiple of 8 KiB.
 // 14 rows whose stride is (nearly) a multiple of 8 KiB land on the same HBM channel/bank set: measured at 2^20 drones, stride mod
@@ -1572,6 +1580,13 @@ int check_device_index(int device)
         return fail(FPV_ENODEV, std::string("no HIP device available: ") + (e != hipSuccess ? hipGetErrorString(e) : "device count is 0"));
     if (device < 0 || device >= count) return fail(FPV_ENODEV, "device index out of range");
     return FPV_OK;
+}
+
+// the kernel constants and the reset jitter of `params` (fpv_derive.h): FPV_OK, or the error code with *why set
+int derive(const fpv_params_t* params, FpvK* K, FpvResetJitter* J, const char** why)
+{
+    const int rc = fpv_derive_constants(params, K, why);
+    return rc == FPV_OK ? fpv_derive_reset_jitter(params, J, why) : rc;
 }
 
 }  // namespace
@@ -1602,21 +1617,13 @@ int fpv_state_rows(int mode)
 int fpv_algorithmic_bytes(int mode)
 {
     if (mode != FPV_MODE_DRONE && mode != FPV_MODE_RACER) return fail(FPV_EINVAL, "unknown mode");
-    const int rows = mode == FPV_MODE_DRONE ? FPV_DRONE_ROWS : 20;   // Racer base rows (181 B); variants: fpv_handle_algorithmic_bytes
-    return rows * 4 * 2 + 16 + 4 + 1;   // state read + write, action read, reward + done write
+    return algorithmic_bytes(mode, nullptr);   // 133; Racer base rows (181 B); variants: fpv_handle_algorithmic_bytes
 }
 
 int fpv_handle_algorithmic_bytes(fpv_handle_t h)
 {
     if (!h) return fail(FPV_EINVAL, "null handle");
-    if (h->mode == FPV_MODE_DRONE && (h->K.flags & FPV_FLAG_FP16_STATE))
-        return (3 * 4 + FPV_HALF_PAIR_ROWS * 4 + 2) * 2 + 16 + 4 + 1;   // 89
-    if (h->mode == FPV_MODE_RACER) {
-        // rows the selected kernel actually moves: 20 base (+6 (hi, lo) rows as written, +3 components.PID)
-        const int rows = 20 + (h->K.r_wide ? 6 : 0) + (h->K.r_pid_variant ? 3 : 0);
-        return rows * 4 * 2 + 16 + 4 + 1;
-    }
-    return fpv_algorithmic_bytes(h->mode);
+    return algorithmic_bytes(h->mode, &h->K);  // the rows the selected kernel actually moves (fp16 state: 89)
 }
 
 int fpv_create(const fpv_params_t* params, int64_t n, int device, fpv_handle_t* out)
@@ -1628,8 +1635,7 @@ int fpv_create(const fpv_params_t* params, int64_t n, int device, fpv_handle_t* 
     FpvK K;
     FpvResetJitter J;
     const char* why = "";
-    int rc = fpv_derive_constants(params, &K, &why);
-    if (rc == FPV_OK) rc = fpv_derive_reset_jitter(params, &J, &why);
+    const int rc = derive(params, &K, &J, &why);
     if (rc != FPV_OK) return fail(rc, why);
     const int drc = check_device_index(device);
     if (drc != FPV_OK) return drc;
@@ -1661,8 +1667,7 @@ int fpv_set_params(fpv_handle_t h, const fpv_params_t* params)
     FpvK K;
     FpvResetJitter J;
     const char* why = "";
-    int rc = fpv_derive_constants(params, &K, &why);
-    if (rc == FPV_OK) rc = fpv_derive_reset_jitter(params, &J, &why);
+    const int rc = derive(params, &K, &J, &why);
     if (rc != FPV_OK) return fail(rc, why);
     h->K = K; h->rj = J; h->P = *params;
     return FPV_OK;
@@ -1716,8 +1721,7 @@ int fpv_reset_pose_sample(const fpv_params_t* params, uint64_t global_id, uint64
     FpvK K;
     FpvResetJitter J;
     const char* why = "";
-    int rc = fpv_derive_constants(params, &K, &why);
-    if (rc == FPV_OK) rc = fpv_derive_reset_jitter(params, &J, &why);
+    const int rc = derive(params, &K, &J, &why);
     if (rc != FPV_OK) return fail(rc, why);
     for (int r = 0; r < 10; ++r) out[r] = base[r];
     if (K.flags & FPV_FLAG_RESET_JITTER) fpv_reset_jitter(J, global_id, step, explicit_reset ? 1u : 0u, out);
@@ -1782,14 +1786,10 @@ int fpv_reset(fpv_handle_t h, const fpv_buffers_t* b, const uint8_t* mask, const
     if (rc != FPV_OK) return rc;
     const DeviceGuard dev(h->device);
     if (dev.rc != FPV_OK) return dev.rc;
-    const dim3 grid((unsigned)((h->n + kBlock - 1) / kBlock));
     FpvBufD d = to_device_view(h, b);
     d.step = h->launches;                // the jitter of an explicit reset is keyed by the handle's step counter
-    hipLaunchKernelGGL(fpv_reset_kernel, grid, dim3(kBlock), 0, (hipStream_t)stream, h->K, d,
-                       h->mode, mask, position, velocity, ypr_deg, h->n);
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return hip_fail(e, "reset kernel launch");
-    return FPV_OK;
+    return launch("reset kernel launch", fpv_reset_kernel, blocks_for(h->n, kBlock), dim3(kBlock), (hipStream_t)stream, h->K, d,
+                  h->mode, mask, position, velocity, ypr_deg, h->n);
 }
 
 int fpv_step(fpv_handle_t h, const fpv_buffers_t* b, void* stream)
@@ -1801,6 +1801,32 @@ int fpv_step(fpv_handle_t h, const fpv_buffers_t* b, void* stream)
     return launch_step(h, to_device_view(h, b), (hipStream_t)stream);
 }
 
+namespace {
+
+void drop_graph(fpv_env* h)
+{
+    if (h->graph_exec) { (void)hipGraphExecDestroy(h->graph_exec); h->graph_exec = nullptr; }
+    if (h->graph) { (void)hipGraphDestroy(h->graph); h->graph = nullptr; }
+    h->graph_nodes.clear();
+    h->graph_shape_key.clear();
+    h->graph_ptr_key.clear();
+}
+
+// step t's device view of a k-step call (fpv_rollout's launches, fpv_rollout_graph's nodes); a null action (stick noise) stays null
+FpvBufD graph_step_view(const fpv_buffers_t* b, const FpvBufD& d0, int t, int64_t action_stride, int64_t out_stride)
+{
+    FpvBufD d = d0;
+    if (b->action) d.action = reinterpret_cast<const float4*>(b->action + (int64_t)t * action_stride);
+    if (out_stride) {
+        if (b->reward) d.reward = b->reward + (int64_t)t * out_stride;
+        if (b->done) d.done = b->done + (int64_t)t * out_stride;
+    }
+    if (b->done_bits) d.done_bits = reinterpret_cast<unsigned long long*>(b->done_bits) + (int64_t)t * b->done_bits_stride;
+    return d;
+}
+
+}  // namespace
+
 int fpv_rollout(fpv_handle_t h, const fpv_buffers_t* b, int k, int64_t action_stride, int64_t out_stride,
                 void* stream)
 {
@@ -1811,28 +1837,16 @@ int fpv_rollout(fpv_handle_t h, const fpv_buffers_t* b, int k, int64_t action_st
     if (b->rotation_override) return fail(FPV_EINVAL, "the guidance override is a per-step input: use fpv_step");
     const DeviceGuard dev(h->device);
     if (dev.rc != FPV_OK) return dev.rc;
-    FpvBufD d = to_device_view(h, b);
-    const float* a0 = b->action;
-    for (int t = 0; t < k; ++t) {
-        d.action = a0 ? reinterpret_cast<const float4*>(a0 + (int64_t)t * action_stride) : nullptr;
-        if (out_stride) {
-            if (b->reward) d.reward = b->reward + (int64_t)t * out_stride;
-            if (b->done) d.done = b->done + (int64_t)t * out_stride;
-        }
-        if (b->done_bits) d.done_bits = reinterpret_cast<unsigned long long*>(b->done_bits) + (int64_t)t * b->done_bits_stride;
-        if ((rc = launch_step(h, d, (hipStream_t)stream)) != FPV_OK) return rc;
-    }
+    const FpvBufD d0 = to_device_view(h, b);
+    for (int t = 0; t < k; ++t)
+        if ((rc = launch_step(h, graph_step_view(b, d0, t, action_stride, out_stride), (hipStream_t)stream)) != FPV_OK) return rc;
     return FPV_OK;
 }
 
 int fpv_diag_stream_copy(float* dst, const float* src, int64_t n_floats, void* stream)
 {
     if (!dst || !src || n_floats <= 0) return fail(FPV_EINVAL, "bad argument");
-    const dim3 grid((unsigned)((n_floats + kBlock - 1) / kBlock));
-    hipLaunchKernelGGL(fpv_diag_copy_kernel, grid, dim3(kBlock), 0, (hipStream_t)stream, dst, src, n_floats);
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return hip_fail(e, "diag copy launch");
-    return FPV_OK;
+    return launch("diag copy launch", fpv_diag_copy_kernel, blocks_for(n_floats, kBlock), dim3(kBlock), (hipStream_t)stream, dst, src, n_floats);
 }
 
 int fpv_diag_stream_copy_wide(float* dst, const float* src, int64_t n_floats, void* stream)
@@ -1840,21 +1854,14 @@ int fpv_diag_stream_copy_wide(float* dst, const float* src, int64_t n_floats, vo
     if (!dst || !src || n_floats <= 0) return fail(FPV_EINVAL, "bad argument");
     if (n_floats % 4 || ((uintptr_t)dst & 15) || ((uintptr_t)src & 15)) return fail(FPV_EALIGN, "n_floats must be a multiple of 4 and both pointers 16-byte aligned");
     const int64_t n4 = n_floats / 4;
-    const dim3 grid((unsigned)((n4 + kBlock - 1) / kBlock));
-    hipLaunchKernelGGL(fpv_diag_copy4_kernel, grid, dim3(kBlock), 0, (hipStream_t)stream, reinterpret_cast<fpv_v4f*>(dst),
-                       reinterpret_cast<const fpv_v4f*>(src), n4);
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return hip_fail(e, "diag wide copy launch");
-    return FPV_OK;
+    return launch("diag wide copy launch", fpv_diag_copy4_kernel, blocks_for(n4, kBlock), dim3(kBlock), (hipStream_t)stream,
+                  reinterpret_cast<fpv_v4f*>(dst), reinterpret_cast<const fpv_v4f*>(src), n4);
 }
 
 int fpv_diag_xcd_map(uint32_t* xcd_of_block, int64_t blocks, void* stream)
 {
     if (!xcd_of_block || blocks <= 0 || blocks > ((int64_t)1 << 24)) return fail(FPV_EINVAL, "fpv_diag_xcd_map: need a device buffer and 0 < blocks <= 2^24");
-    hipLaunchKernelGGL(fpv_diag_xcd_kernel, dim3((unsigned)blocks), dim3(kStepBlock), 0, (hipStream_t)stream, xcd_of_block);
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return hip_fail(e, "diag xcd-map launch");
-    return FPV_OK;
+    return launch("diag xcd-map launch", fpv_diag_xcd_kernel, dim3((unsigned)blocks), dim3(kStepBlock), (hipStream_t)stream, xcd_of_block);
 }
 
 int fpv_diag_busy(double microseconds, void* stream)
@@ -1866,10 +1873,7 @@ int fpv_diag_busy(double microseconds, void* stream)
         khz = 100000;
     const unsigned long long ticks = (unsigned long long)(microseconds * (double)khz * 1e-3);
     // one s_sleep(32) is 32 x 64 clocks ~ 1 us at 2 GHz: the iteration cap is ~4x the requested time
-    hipLaunchKernelGGL(fpv_diag_busy_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, ticks, (int)(microseconds * 4.0) + 64);
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return hip_fail(e, "diag busy launch");
-    return FPV_OK;
+    return launch("diag busy launch", fpv_diag_busy_kernel, dim3(1), dim3(64), (hipStream_t)stream, ticks, (int)(microseconds * 4.0) + 64);
 }
 
 int fpv_step_n(fpv_handle_t h, const fpv_buffers_t* b, int k, int64_t action_stride, int64_t out_stride, void* stream)
@@ -1886,45 +1890,8 @@ int fpv_step_n(fpv_handle_t h, const fpv_buffers_t* b, int k, int64_t action_str
     if (dev.rc != FPV_OK) return dev.rc;
     FpvBufD d = to_device_view(h, b);
     d.step = h->launches;
-    FpvRoll R;
-    R.k = k; R.pad = 0; R.action_stride = action_stride; R.out_stride = out_stride; R.bits_stride = b->done_bits_stride;
-    const RollKernel f = choose_rollout_kernel(h, d);
-    const unsigned grid = (unsigned)((h->n + kStepBlock - 1) / kStepBlock);
-    FpvRollArgs args;
-    memset(&args, 0, sizeof(args));
-    args.K = h->K; args.B = d; args.n = h->n; args.R = R;
-    hipLaunchKernelGGL(f, dim3(grid), dim3(kStepBlock), 0, (hipStream_t)stream, args);
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return hip_fail(e, "k-step kernel launch");
-    h->launches += (uint64_t)k;
-    return FPV_OK;
+    return launch_roll(h, d, FpvRoll{k, 0, action_stride, out_stride, b->done_bits_stride}, (hipStream_t)stream, "k-step kernel launch");
 }
-
-namespace {
-
-void drop_graph(fpv_env* h)
-{
-    if (h->graph_exec) { (void)hipGraphExecDestroy(h->graph_exec); h->graph_exec = nullptr; }
-    if (h->graph) { (void)hipGraphDestroy(h->graph); h->graph = nullptr; }
-    h->graph_nodes.clear();
-    h->graph_shape_key.clear();
-    h->graph_ptr_key.clear();
-}
-
-// step t's device view of a k-step graph
-FpvBufD graph_step_view(const fpv_buffers_t* b, const FpvBufD& d0, int t, int64_t action_stride, int64_t out_stride)
-{
-    FpvBufD d = d0;
-    d.action = reinterpret_cast<const float4*>(b->action + (int64_t)t * action_stride);
-    if (out_stride) {
-        if (b->reward) d.reward = b->reward + (int64_t)t * out_stride;
-        if (b->done) d.done = b->done + (int64_t)t * out_stride;
-    }
-    if (b->done_bits) d.done_bits = reinterpret_cast<unsigned long long*>(b->done_bits) + (int64_t)t * b->done_bits_stride;
-    return d;
-}
-
-}  // namespace
 
 int fpv_rollout_graph(fpv_handle_t h, const fpv_buffers_t* b, int k, int64_t action_stride, int64_t out_stride,
                       void* stream)
@@ -1945,34 +1912,25 @@ int fpv_rollout_graph(fpv_handle_t h, const fpv_buffers_t* b, int k, int64_t act
     if (dev.rc != FPV_OK) return dev.rc;
     const FpvBufD d0 = to_device_view(h, b);
     // SHAPE of the graph: everything that selects kernels, grids and non-pointer arguments
-    const KernelChoice c0 = choose_kernel(h, d0);
+    const StepKernel f0 = choose_kernel(h, d0);
     std::string shape(reinterpret_cast<const char*>(&h->K), sizeof(h->K));
     const int64_t meta[7] = {k, action_stride, out_stride, h->n, b->ld, b->action_ld, b->done_bits_stride};
     shape.append(reinterpret_cast<const char*>(meta), sizeof(meta));
-    shape.append(reinterpret_cast<const char*>(&c0.func), sizeof(c0.func));
+    shape.append(reinterpret_cast<const char*>(&f0), sizeof(f0));
     shape.append(reinterpret_cast<const char*>(&d0.objs), sizeof(d0.objs));
     const float wind[3] = {d0.wx, d0.wy, d0.wz};
     shape.append(reinterpret_cast<const char*>(wind), sizeof(wind));
     // everything else in the view is a buffer address
     const std::string ptrs(reinterpret_cast<const char*>(&d0), sizeof(d0));
-    FpvK K = h->K;
     if (!h->graph_exec || shape != h->graph_shape_key) {
         drop_graph(h);
         hipError_t e = hipGraphCreate(&h->graph, 0);
         if (e != hipSuccess) { drop_graph(h); return hip_fail(e, "hipGraphCreate"); }
         hipGraphNode_t prev = nullptr;
         for (int t = 0; t < k; ++t) {
-            FpvBufD d = graph_step_view(b, d0, t, action_stride, out_stride);
-            const KernelChoice c = choose_kernel(h, d);
-            int64_t n_start = graph_n_start(h, c, d, t);
-            void* args[8] = {&d.state, &d.ld, &d.action, &d.action_ld, &d.state_h, &n_start, &K, &d};   // copied by hipGraphAddKernelNode
-            hipKernelNodeParams np;
-            memset(&np, 0, sizeof(np));
-            np.func = reinterpret_cast<void*>(c.func);
-            np.gridDim = dim3(c.grid); np.blockDim = dim3(c.block);
-            np.sharedMemBytes = 0; np.kernelParams = args; np.extra = nullptr;
+            const GraphNode g(h, graph_step_view(b, d0, t, action_stride, out_stride), t);
             hipGraphNode_t node;
-            e = hipGraphAddKernelNode(&node, h->graph, prev ? &prev : nullptr, prev ? 1 : 0, &np);
+            e = hipGraphAddKernelNode(&node, h->graph, prev ? &prev : nullptr, prev ? 1 : 0, &g.np);
             if (e != hipSuccess) { drop_graph(h); return hip_fail(e, "hipGraphAddKernelNode"); }
             h->graph_nodes.push_back(node);
             prev = node;
@@ -1984,16 +1942,8 @@ int fpv_rollout_graph(fpv_handle_t h, const fpv_buffers_t* b, int k, int64_t act
     } else if (ptrs != h->graph_ptr_key) {
         // same shape, new buffers (e.g. a fresh actions tensor every call): patch the node arguments
         for (int t = 0; t < k; ++t) {
-            FpvBufD d = graph_step_view(b, d0, t, action_stride, out_stride);
-            const KernelChoice c = choose_kernel(h, d);
-            int64_t n_start = graph_n_start(h, c, d, t);
-            void* args[8] = {&d.state, &d.ld, &d.action, &d.action_ld, &d.state_h, &n_start, &K, &d};
-            hipKernelNodeParams np;
-            memset(&np, 0, sizeof(np));
-            np.func = reinterpret_cast<void*>(c.func);
-            np.gridDim = dim3(c.grid); np.blockDim = dim3(c.block);
-            np.sharedMemBytes = 0; np.kernelParams = args; np.extra = nullptr;
-            const hipError_t e = hipGraphExecKernelNodeSetParams(h->graph_exec, h->graph_nodes[(size_t)t], &np);
+            const GraphNode g(h, graph_step_view(b, d0, t, action_stride, out_stride), t);
+            const hipError_t e = hipGraphExecKernelNodeSetParams(h->graph_exec, h->graph_nodes[(size_t)t], &g.np);
             if (e != hipSuccess) { drop_graph(h); return hip_fail(e, "hipGraphExecKernelNodeSetParams"); }
         }
         h->graph_ptr_key = ptrs;
@@ -2013,11 +1963,8 @@ int fpv_widen_state(fpv_handle_t h, const fpv_buffers_t* b, float* out, int64_t 
     const DeviceGuard dev(h->device);
     if (dev.rc != FPV_OK) return dev.rc;
     const uint16_t* thrust = b->state_h_thrust ? b->state_h_thrust : b->state_h + (int64_t)2 * FPV_HALF_PAIR_ROWS * b->ld;
-    hipLaunchKernelGGL(fpv_widen_state_kernel, dim3((unsigned)((h->n + kBlock - 1) / kBlock)), dim3(kBlock), 0, (hipStream_t)stream,
-                       b->state, b->state_h, thrust, b->ld, out, out_ld, h->n);
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return hip_fail(e, "widen kernel launch");
-    return FPV_OK;
+    return launch("widen kernel launch", fpv_widen_state_kernel, blocks_for(h->n, kBlock), dim3(kBlock), (hipStream_t)stream,
+                  b->state, b->state_h, thrust, b->ld, out, out_ld, h->n);
 }
 
 int fpv_return_triple(fpv_handle_t h, const fpv_buffers_t* b, float* rt, float* gyro, float* acc, void* stream)
@@ -2029,11 +1976,8 @@ int fpv_return_triple(fpv_handle_t h, const fpv_buffers_t* b, float* rt, float* 
     if (acc && !b->accel) return fail(FPV_EINVAL, "R @ acceleration needs fpv_buffers_t.accel (the step kernel writes it there)");
     const DeviceGuard dev(h->device);
     if (dev.rc != FPV_OK) return dev.rc;
-    hipLaunchKernelGGL(fpv_return_triple_kernel, dim3((unsigned)((h->n + kBlock - 1) / kBlock)), dim3(kBlock), 0, (hipStream_t)stream,
-                       b->state, b->ld, b->accel, rt, gyro, acc, h->n);
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return hip_fail(e, "return-triple kernel launch");
-    return FPV_OK;
+    return launch("return-triple kernel launch", fpv_return_triple_kernel, blocks_for(h->n, kBlock), dim3(kBlock), (hipStream_t)stream,
+                  b->state, b->ld, b->accel, rt, gyro, acc, h->n);
 }
 
 int fpv_pid_reset(float* pid_state, int64_t ld, int64_t n, const uint8_t* mask, int device, void* stream)
@@ -2044,11 +1988,7 @@ int fpv_pid_reset(float* pid_state, int64_t ld, int64_t n, const uint8_t* mask, 
     if (rc != FPV_OK) return rc;
     const DeviceGuard dev(device);
     if (dev.rc != FPV_OK) return dev.rc;
-    hipLaunchKernelGGL(fpv_pid_reset_kernel, dim3((unsigned)((n + kBlock - 1) / kBlock)), dim3(kBlock), 0, (hipStream_t)stream,
-                       pid_state, ld, n, mask);
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return hip_fail(e, "pid reset kernel launch");
-    return FPV_OK;
+    return launch("pid reset kernel launch", fpv_pid_reset_kernel, blocks_for(n, kBlock), dim3(kBlock), (hipStream_t)stream, pid_state, ld, n, mask);
 }
 
 int fpv_pid_call(const fpv_pid_params_t* params, float* pid_state, int64_t ld, int64_t n, const float* current,
@@ -2071,11 +2011,8 @@ int fpv_pid_call(const fpv_pid_params_t* params, float* pid_state, int64_t ld, i
     P.gain[0][0] = (float)params->kP; P.gain[0][1] = (float)params->kI; P.gain[0][2] = (float)params->kD;
     P.integral_clip = (float)params->integral_clip; P.min_output = (float)params->min_output; P.max_output = (float)params->max_output;
     P.d_rate = (float)params->derivative_transition_rate; P.om_d_rate = (float)(1.0 - params->derivative_transition_rate);
-    hipLaunchKernelGGL(fpv_pid_kernel, dim3((unsigned)((n + kBlock - 1) / kBlock)), dim3(kBlock), 0, (hipStream_t)stream,
-                       P, pid_state, ld, n, current, target, target_scalar, out, error_out);
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return hip_fail(e, "pid kernel launch");
-    return FPV_OK;
+    return launch("pid kernel launch", fpv_pid_kernel, blocks_for(n, kBlock), dim3(kBlock), (hipStream_t)stream,
+                  P, pid_state, ld, n, current, target, target_scalar, out, error_out);
 }
 
 // ---- RCCL, opened at run time ------------------------------------------------------------------------------

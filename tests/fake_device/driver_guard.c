@@ -1,7 +1,7 @@
 /* The scoped device binding of every launching entry point (DeviceGuard, csrc/fpv_hip.hip) on a host with TWO devices - which the
  * builder's boxes never had: a handle created on device 1 is used while the thread's current device is 0.  The preloaded stand-in
- * runtime (fake_hip.c) records hipSetDevice; the launch itself then fails in the real runtime (there is no GPU here), which is the
- * point: even on the error path the caller's device is put back.  Prints one line of JSON for tests/test_device_guard.py. */
+ * runtime (fake_hip.c) records hipSetDevice and refuses the launch itself, which is the point: even on the error path the caller's
+ * device is put back.  Prints one line of JSON for tests/test_device_guard.py. */
 #define _GNU_SOURCE
 #include <dlfcn.h>
 #include <stdint.h>

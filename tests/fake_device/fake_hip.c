@@ -1,7 +1,8 @@
 /* A stand-in for the four HIP runtime calls that fpv_create / fpv_device_cache_model make, preloaded (LD_PRELOAD) in front of
  * libamdhip64 by tests/test_device_guard.py: the device's answers come from the environment, so the library's reaction to a device
  * that is NOT the one its cache model was measured on - a CPX compute partition, another architecture - is tested without owning
- * such a device (and without any GPU).  No kernel is launched through it: the driver only creates handles and asks them. */
+ * such a device (and without any GPU).  It also refuses every kernel launch, so that a driver stepping a handle with fabricated
+ * buffer addresses never reaches a real device, on a host that has one. */
 #include <stdlib.h>
 #include <string.h>
 
@@ -37,3 +38,11 @@ hipError_t hipGetDevicePropertiesR0600(hipDeviceProp_tR0600* prop, int device)
     prop->l2CacheSize = env_int("FAKE_HIP_L2", 4 << 20);
     return hipSuccess;
 }
+
+/* no launch leaves the process: the library sees what a host without a device reports (hip_fail: FPV_ENODEV) */
+hipError_t hipLaunchKernel(const void* function_address, dim3 grid, dim3 block, void** args, size_t shared_bytes, hipStream_t stream)
+{
+    (void)function_address; (void)grid; (void)block; (void)args; (void)shared_bytes; (void)stream;
+    return hipErrorNoDevice;
+}
+hipError_t hipGetLastError(void) { return hipErrorNoDevice; }

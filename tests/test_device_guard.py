@@ -86,7 +86,7 @@ def test_launching_calls_bind_the_handles_device_and_put_the_callers_back(tmp_pa
     """DeviceGuard (csrc/fpv_hip.hip) on a host with TWO devices - its switch branch never ran on the builder's one-GPU boxes
     (Missing #4).  The stand-in runtime reports two devices and records hipSetDevice; a handle created on device 1 is
     stepped while the caller's device is 0: the library switches to 1 and back to 0 - also though the launch itself then fails
-    (there is no GPU under it here: FPV_ENODEV), i.e. on the error path; a handle on the caller's own device causes no switch."""
+    (the stand-in refuses every launch: FPV_ENODEV), i.e. on the error path; a handle on the caller's own device causes no switch."""
     so, exe, blob = str(tmp_path / "libfake_hip.so"), str(tmp_path / "driver_guard"), str(tmp_path / "params.bin")
     subprocess.run(["gcc", "-O1", "-shared", "-fPIC", "-I/opt/rocm/include", "-o", so, os.path.join(FAKE, "fake_hip.c")], check=True)
     subprocess.run(["gcc", "-O1", "-o", exe, os.path.join(FAKE, "driver_guard.c"), "-L" + os.path.join(REPO, "fpyv_amd"), "-lfpv_hip", "-ldl",
