@@ -623,7 +623,13 @@ class _Partition:
             return None
         st = self.parent.state
         if type(action) is torch.Tensor and action.dtype in (torch.float16, torch.bfloat16, torch.float64) and action.device == st.device:
-            action = self.parent._cast_sticks(action)      # as step() and rollout() do
+            # as step() and rollout() do, but on THIS partition's stream, after step_async's wait (ready=True makes none: the
+            # caller has said the input is complete): the float32 copy is written before the step reads it, and it is allocated
+            # from and freed to this stream's pool, so it is not handed out again before the step is through.  The input is read
+            # there too: record_stream keeps the caller's pool from handing it out again before the cast has run.
+            action.record_stream(self.stream)
+            with torch.cuda.stream(self.stream):
+                action = self.parent._cast_sticks(action)
         if type(action) is torch.Tensor and action.dtype is torch.float32 and action.device == st.device:
             if action.shape == self._ashape and action.is_contiguous():               # [n_p, 4] rows (a row slice of [N, 4] is one)
                 self._buf.action_ld = 0
@@ -1076,7 +1082,12 @@ class FpvVecEnv:
         """Enqueue one step of partition `part` on its own stream and return at once.  `action`: this partition's sticks,
         [n_p, 4] rows or [4, n_p] SoA (slices of full-size tensors qualify).  The step is ordered after whatever the
         caller's current stream has enqueued so far (the policy that produced `action`), unless that IS the partition's
-        stream or `ready=True` says the tensor is already complete (pre-generated sticks)."""
+        stream or `ready=True` says the tensor is already complete (pre-generated sticks).
+
+        The step reads a float32 `action` in place on the partition's stream: keep the tensor alive, and do not write it on the
+        caller's stream, until the step_wait(part) of this step (the loop step_wait -> policy -> step_async does).  Sticks of
+        another floating dtype (float16, bfloat16, float64) are cast to float32 on the partition's stream, after the wait, into
+        a copy that stream owns; such an input must not be written before step_wait(part) either, but it may be dropped at once."""
         P = self._part(part)
         if not ready:
             cur = torch.cuda.current_stream(self.batch.device)

@@ -10,6 +10,20 @@ from parity import REL_TOL, assert_parity, soa_vs_oracle  # noqa: F401
 DEV = "cuda:0"
 
 
+def hold(stream, us=5000.0):
+    """Hold `stream` back for about `us` microseconds: a chain of fpv_diag_busy kernels (one wave each, ends on its own time
+    bound, at most 1000 us apiece - the ABI's limit) enqueued on it.  What is enqueued on that stream afterwards starts only when
+    the chain is through; other streams run meanwhile.  It turns a race between two streams into a fixed order: hold the producer
+    and a consumer that is not ordered after it reads its input early; hold the consumer and a buffer that went back to another
+    stream's pool too early is overwritten before it is read."""
+    L = _lib.lib()
+    left = float(us)
+    while left > 0:
+        chunk = min(left, 1000.0)
+        _lib.check(L.fpv_diag_busy(chunk, stream.cuda_stream))
+        left -= chunk
+
+
 def _drone_batch(p, n, **kw):
     from fpyv_amd.env import DroneBatch
     return DroneBatch(p, n, device=DEV, **kw)
