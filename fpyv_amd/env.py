@@ -41,7 +41,173 @@ def _round_up(x: int, m: int) -> int:
     return (x + m - 1) // m * m
 
 
-class _Batch:
+def _set_wind(buf: _lib.FpvBuffers, wind: Sequence[float]) -> None:
+    w = buf.wind
+    w[0], w[1], w[2] = float(wind[0]), float(wind[1]), float(wind[2])
+
+
+class _Handle:
+    """One C handle (fpv_create) of `n` drones and the fpv_buffers_t its launches read: what a batch and each of its
+    partitions own alike.  `pack_kw` holds what pack_params takes besides the params and auto_reset, the global drone-id
+    offset of the first drone included.  The subclass points `_buf` at its tensors."""
+
+    _coerce = True              # the single batch turns any stick argument into [n, 4] float32 rows; a partition does not
+    _warned_cast = False
+
+    def __init__(self, params: DroneParams, n: int, device: torch.device, dev_index: int, auto_reset: bool,
+                 pack_kw: Dict[str, Any]):
+        self.n, self.device, self._dev_index = n, device, dev_index
+        self._dev = torch.device("cuda", dev_index)
+        self.stick_noise, self._pack_kw = bool(pack_kw["stick_noise"]), pack_kw
+        self._L = _lib.lib()
+        self._handle = C.c_void_p()
+        cp = self._pack(params, auto_reset)
+        _lib.check(self._L.fpv_create(C.byref(cp), n, dev_index, C.byref(self._handle)))
+        self.params, self._cparams = params, cp
+        self._buf = _lib.FpvBuffers()
+        self._buf_ref = C.byref(self._buf)
+        self._fpv_step = self._L.fpv_step
+        self._steps_launched = 0        # mirrors the handle's launch counter (fpv_set_step_counter)
+        self._ashape = torch.Size((n, 4))
+        self._keepalive = self._last_action = self._bcast_action = None
+        self._last_action_ptr = 0
+
+    def _pack(self, params: DroneParams, auto_reset: bool) -> _lib.FpvParams:
+        return _lib.pack_params(params, auto_reset=auto_reset, **self._pack_kw)
+
+    @property
+    def _auto_reset(self) -> bool:
+        return bool(self._cparams.flags & _lib.FPV_FLAG_AUTO_RESET)
+
+    def set_params(self, params: DroneParams, auto_reset: Optional[bool] = None) -> None:
+        cp = self._pack(params, self._auto_reset if auto_reset is None else auto_reset)
+        _lib.check(self._L.fpv_set_params(self._handle, C.byref(cp)))
+        self.params, self._cparams = params, cp
+
+    def set_step_counter(self, step: int) -> None:
+        """64-bit step index keying the stick-noise stream / stochastic rounding (counts the steps launched, from 0)."""
+        if not 0 <= int(step) < 2 ** 64:
+            raise ValueError("the step counter is an unsigned 64-bit integer")
+        _lib.check(self._L.fpv_set_step_counter(self._handle, int(step)))
+        self._steps_launched = int(step)
+
+    def close(self) -> None:
+        if getattr(self, "_handle", None) is not None and self._handle.value:
+            self._L.fpv_destroy(self._handle)
+            self._handle = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def _stream(self) -> int:
+        """hipStream_t of torch's current stream on this device (raw handle; ~5x cheaper than building
+        a torch.cuda.Stream object on every step)."""
+        try:
+            return torch._C._cuda_getCurrentRawStream(self._dev_index)
+        except AttributeError:                       # private fast path gone in some future torch
+            return torch.cuda.current_stream(self.device).cuda_stream
+
+    def _step_raw(self, action: Any, wind: Optional[Sequence[float]] = None,
+                  stream: Optional[torch.cuda.Stream] = None) -> None:
+        """One step: `action` through the stick intake, `wind` bound (None: the bound one stays), one fpv_step on `stream`
+        (None: torch's current stream), the mirrored launch counter advanced modulo 2^64."""
+        b = self._buf
+        self._keepalive, b.action, b.action_ld = self._sticks(action, stream)
+        if wind is not None:
+            _set_wind(b, wind)
+        rc = self._fpv_step(self._handle, self._buf_ref, self._stream() if stream is None else stream.cuda_stream)
+        if rc < 0:
+            _lib.check(rc)
+        self._steps_launched = (self._steps_launched + 1) & 0xFFFFFFFFFFFFFFFF
+
+    def _sticks(self, action: Any, stream: Optional[torch.cuda.Stream] = None,
+                block: bool = False) -> Tuple[Optional[torch.Tensor], Optional[int], int]:
+        """The stick intake of every launch: (the tensor the launch reads, which the caller keeps alive; its address;
+        action_ld).  `stream` launches the step (None: torch's current stream).
+          None                                in-kernel noise sticks (stick_noise=True only)
+          float32 [n, 4], contiguous          read in place, action_ld 0; the very tensor object of the previous call, still
+                                              at the same address (a policy that writes its output in place), is not checked again
+          float32 [4, n], unit column stride  SoA (e.g. the output of `W @ obs_soa`), read in place, action_ld = stride(0)
+          float16 / bfloat16 / float64        cast to float32 on the device, then as above
+          anything else                       the single batch coerces it (`_coerce_action`); a partition raises
+        block=True takes a rollout's sticks - [k, n, 4] or held rows, not checked here -: contiguous float32 or cast."""
+        if action is None:
+            if not self.stick_noise:
+                raise ValueError("action=None is only meaningful with stick_noise=True (pure noise sticks)")
+            return None, None, 0
+        if action is self._last_action and action.data_ptr() == self._last_action_ptr and action.shape == self._ashape:
+            return action, self._last_action_ptr, 0
+        self._last_action = None
+        if type(action) is torch.Tensor and action.dtype is torch.float32 and action.device == self._dev:
+            if action.shape == self._ashape and action.is_contiguous():
+                self._last_action, self._last_action_ptr = action, action.data_ptr()
+                return action, self._last_action_ptr, 0
+            if (not block and action.dim() == 2 and action.shape[0] == 4 and action.shape[1] == self.n != 4
+                    and action.stride(1) == 1 and action.stride(0) >= self.n):
+                return action, action.data_ptr(), action.stride(0)
+        elif (torch.is_tensor(action) and action.dtype in (torch.float16, torch.bfloat16, torch.float64)
+              and action.device == self._dev
+              and (block or (action.shape == self._ashape if self._coerce else type(action) is torch.Tensor))):
+            # the single batch casts its [n, 4] rows (a [4] broadcast and a wrong shape go to the coercion below); a
+            # partition casts any plain tensor and takes the result in either layout; a rollout casts its whole block
+            return self._sticks(self._cast_sticks(action, stream), stream, block)
+        if block:
+            if torch.is_tensor(action) and action.dtype is torch.float32 and action.is_contiguous() and action.device == self._dev:
+                return action, action.data_ptr(), 0
+            raise ValueError("actions must be a contiguous float32 tensor on the env's device (float16 / bfloat16 / float64 "
+                             "tensors there are cast once per call)")
+        if not self._coerce:
+            raise ValueError(f"a partition's action is a float32 tensor on the env's device, [{self.n}, 4] contiguous rows or "
+                             f"[4, {self.n}] with unit column stride (slices of a full-size tensor qualify)")
+        action = self._coerce_action(action)
+        return action, action.data_ptr(), 0
+
+    def _coerce_action(self, action: Any) -> torch.Tensor:
+        """Whatever the reference's callers pass as sticks - a list, a NumPy array, a [4] broadcast, a tensor of another
+        dtype / device / stride - as a contiguous float32 [num_envs, 4] tensor on the env's device (a copy only if needed)."""
+        if not torch.is_tensor(action):
+            action = torch.as_tensor(np.asarray(action, dtype=np.float32), device=self.device)
+        if action.dim() == 1:
+            if action.numel() != 4:
+                raise ValueError("action must be [4] or [num_envs, 4]")
+            if self._bcast_action is None:
+                self._bcast_action = torch.empty((self.n, 4), dtype=torch.float32, device=self.device)
+            self._bcast_action.copy_(action.to(device=self.device, dtype=torch.float32).expand(self.n, 4))
+            action = self._bcast_action
+        if action.shape != (self.n, 4):
+            raise ValueError(f"action must have shape ({self.n}, 4), got {tuple(action.shape)}")
+        if action.dtype != torch.float32 or action.device != self._dev or not action.is_contiguous():
+            action = action.to(device=self.device, dtype=torch.float32).contiguous()
+        return action
+
+    def _cast_sticks(self, action: torch.Tensor, stream: Optional[torch.cuda.Stream]) -> torch.Tensor:
+        """A stick tensor of another floating dtype as contiguous float32: one cast kernel per call, warned about once (a
+        half-precision policy that cares writes `.float()` into a preallocated buffer itself).  The cast runs on `stream`, the
+        one that launches the step, after that stream's wait, so the copy is written before the step reads it; it is allocated
+        from and freed to that stream's pool, so it is not handed out again before the step is through.  When that is not the
+        current stream, the input is recorded on it: the caller's pool must not hand it out again before the cast has read it."""
+        if not _Handle._warned_cast:
+            import warnings
+            warnings.warn(f"sticks of dtype {action.dtype} are cast to float32 on every call (the kernels read float32 sticks since ABI 6)",
+                          RuntimeWarning, stacklevel=3)
+            _Handle._warned_cast = True
+        if stream is not None and stream != torch.cuda.current_stream(self._dev):
+            action.record_stream(stream)
+        with torch.cuda.stream(stream):                  # None: the current stream
+            return action.to(torch.float32).contiguous()
+
+    def _widen(self, cols: int) -> torch.Tensor:
+        """fp16 storage decoded into a fresh float32 [14, cols] tensor: one launch of fpv_widen_state on torch's current stream,
+        a copy valid for as long as the caller keeps it."""
+        wide = torch.empty((_lib.FPV_DRONE_ROWS, cols), dtype=torch.float32, device=self.device)
+        _lib.check(self._L.fpv_widen_state(self._handle, self._buf_ref, wide.data_ptr(), cols, self._stream()))
+        return wide
+
+
+class _Batch(_Handle):
     """Owns the SoA state tensor and the C handle of one shard of drones on one GPU."""
 
     def __init__(self, params: DroneParams, num_envs: int, device: Any = "cuda:0", auto_reset: bool = False,
@@ -51,26 +217,19 @@ class _Batch:
                  with_action_out: bool = False, kahan_position: bool = False, per_drone_reset_pose: bool = False):
         if num_envs <= 0:
             raise ValueError("num_envs must be positive")
-        self.params = params
-        self.n = int(num_envs)
-        self.device = torch.device(device)
-        if self.device.type != "cuda":
+        device = torch.device(device)
+        if device.type != "cuda":
             raise ValueError("fpyv_amd runs on the GPU only (device must be cuda:N); there is no CPU path")
-        self._L = _lib.lib()
         self.mode = int(params.mode)
         self.rows = _lib.state_rows(self.mode)
-        dev_index = self.device.index if self.device.index is not None else torch.cuda.current_device()
-        self._dev_index = int(dev_index)
+        dev_index = int(device.index if device.index is not None else torch.cuda.current_device())
         # the row stride for THIS device: the L2-aware rule on the MI355X it was measured on, the model-free one elsewhere
-        self.ld = int(_lib.check(self._L.fpv_recommended_ld_device(self.n, self._dev_index)))
-        self._handle = C.c_void_p()
+        self.ld = int(_lib.check(_lib.lib().fpv_recommended_ld_device(int(num_envs), dev_index)))
         self.fp16_state = bool(fp16_state)
         self.rounding_seed = int(rounding_seed) & 0xFFFFFFFF
-        self.stick_noise = bool(stick_noise)
-        self._pack_kw = dict(fp16_state=self.fp16_state, stick_noise=self.stick_noise, noise_seed=noise_seed,
-                             drone_id_offset=drone_id_offset)
-        self._cparams = _lib.pack_params(params, auto_reset=auto_reset, **self._pack_kw)
-        _lib.check(self._L.fpv_create(C.byref(self._cparams), self.n, dev_index, C.byref(self._handle)))
+        super().__init__(params, int(num_envs), device, dev_index, auto_reset,
+                         dict(fp16_state=self.fp16_state, stick_noise=bool(stick_noise), noise_seed=noise_seed,
+                              drone_id_offset=drone_id_offset))
         f32 = dict(dtype=torch.float32, device=self.device)
         if self.fp16_state:
             # BASELINE config 4: position rows fp32; the rest as eleven 16-bit words: five rows of word pairs
@@ -112,17 +271,10 @@ class _Batch:
                 raise ValueError("per_drone_reset_pose is a drone-mode option (the Racer resets to its zero state)")
             self.reset_pose = torch.empty((_lib.RESET_POSE_ROWS, self.ld), **f32)
             self.reset_pose.copy_(torch.from_numpy(self._init_pose()).view(-1, 1).expand(_lib.RESET_POSE_ROWS, self.ld))
-        self._bcast_action = None
         self._objects = None            # the bound fpv_objects_t (None = no collision world bound)
         self._object_rows = None
-        self._last_action, self._last_action_ptr = None, 0
         self._override_keep = None
         self._done_bits_keep = None
-        self._ashape = torch.Size((self.n, 4))
-        self._steps_launched = 0        # mirrors the handle's launch counter (fpv_set_step_counter)
-        self._buf = _lib.FpvBuffers()
-        self._buf_ref = C.byref(self._buf)
-        self._fpv_step = self._L.fpv_step
         self._fill_buffers()
 
     # -- plumbing ---------------------------------------------------------------------------------
@@ -152,105 +304,24 @@ class _Batch:
     def rows_f32(self, r0: int, r1: int) -> torch.Tensor:
         """[num_envs, r1-r0] fp32 values of state rows r0..r1-1 (fpv_abi.h row numbering), whatever the
         storage format; a zero-copy view for fp32 storage, a converted copy for fp16 rows."""
-        if not self.fp16_state:
+        if not self.fp16_state or r1 <= 3:
             return self.state[r0:r1, :self.n].t()
-        if r1 <= 3:
-            return self.state[r0:r1, :self.n].t()
-        # one launch (fpv_widen_state) into a fresh [14, ld] tensor: a copy, like before, valid for as long as the caller keeps it
-        wide = torch.empty((_lib.FPV_DRONE_ROWS, self.ld), dtype=torch.float32, device=self.device)
-        _lib.check(self._L.fpv_widen_state(self._handle, self._buf_ref, wide.data_ptr(), self.ld, self._stream()))
-        return wide[r0:r1, :self.n].t()
+        return self._widen(self.ld)[r0:r1, :self.n].t()
 
     def storage_words(self) -> torch.Tensor:
         """[11, ld] int16: the eleven 16-bit storage words of every drone of an fp16-state batch in storage order - vx vy vz
         (binary16), v_low (three 5-bit low words), qa qb qc (smallest-three 15-bit fixed point + index bits), rx ry rz
         thrust (binary16) - a copy assembled from the five pair rows and the thrust row of `state_h`.  The decoded fp32
         values are `rows_f32` (one launch of fpv_widen_state)."""
-        ld, npair = self.ld, _lib.FPV_HALF_PAIR_ROWS
-        raw = self.state_h.view(torch.int16)
-        pairs = raw[:2 * npair * ld].view(npair, ld, 2).permute(0, 2, 1).reshape(2 * npair, ld)
-        return torch.cat([pairs, raw[2 * npair * ld:].view(1, ld)], dim=0)
+        return self._storage_words(self.ld)
+
+    def _storage_words(self, cols: int) -> torch.Tensor:
+        """[11, cols] int16 copy of the words of drones 0..cols-1 in storage order: five pair rows interleaved, then thrust"""
+        pairs, thrust = self._state_h_views()
+        return torch.cat([pairs[:, :cols].permute(0, 2, 1).reshape(-1, cols), thrust[:cols].view(1, cols)], dim=0)
 
     def algorithmic_bytes(self) -> int:
         return int(self._L.fpv_handle_algorithmic_bytes(self._handle))
-
-    def _stream(self) -> int:
-        """hipStream_t of torch's current stream on this device (raw handle; ~5x cheaper than building
-        a torch.cuda.Stream object on every step)."""
-        try:
-            return torch._C._cuda_getCurrentRawStream(self._dev_index)
-        except AttributeError:                       # private fast path gone in some future torch
-            return torch.cuda.current_stream(self.device).cuda_stream
-
-    def _action_ptr(self, action: Any) -> Optional[int]:
-        if action is None:
-            if not self.stick_noise:
-                raise ValueError("action=None is only meaningful with stick_noise=True (pure noise sticks)")
-            return None
-        # hottest path: the very tensor object of the previous step (a policy that writes its output in place), still at
-        # the same address: everything below was checked then
-        if action is self._last_action and action.data_ptr() == self._last_action_ptr and action.shape == self._ashape:
-            self._keepalive = action                 # a rollout in between may have replaced what `throttle` reports
-            return self._last_action_ptr
-        self._last_action = None
-        # hot path: a contiguous float32 [num_envs, 4] tensor on the env's device
-        if (type(action) is torch.Tensor and action.dtype is torch.float32 and action.shape == self._ashape
-                and action.is_contiguous() and action.device == self.state.device):
-            self._keepalive = action
-            self._buf.action_ld = 0
-            self._last_action, self._last_action_ptr = action, action.data_ptr()
-            return self._last_action_ptr
-        # SoA sticks [4, num_envs] (e.g. the output of `W @ obs_soa`): consumed in place, no transpose
-        if (type(action) is torch.Tensor and action.dim() == 2 and action.shape[0] == 4 and action.shape[1] == self.n
-                and self.n != 4 and action.dtype is torch.float32 and action.stride(1) == 1 and action.stride(0) >= self.n
-                and action.device == self.state.device):
-            self._keepalive = action
-            self._buf.action_ld = action.stride(0)
-            return action.data_ptr()
-        self._buf.action_ld = 0
-        action = self._coerce_action(action)
-        self._keepalive = action
-        return action.data_ptr()
-
-    def _coerce_action(self, action: Any) -> torch.Tensor:
-        """Whatever the reference's callers pass as sticks - a list, a NumPy array, a [4] broadcast, a tensor of another
-        dtype / device / stride - as a contiguous float32 [num_envs, 4] tensor on the env's device (a copy only if needed)."""
-        if not torch.is_tensor(action):
-            action = torch.as_tensor(np.asarray(action, dtype=np.float32), device=self.device)
-        if action.dim() == 1:
-            if action.numel() != 4:
-                raise ValueError("action must be [4] or [num_envs, 4]")
-            if self._bcast_action is None:
-                self._bcast_action = torch.empty((self.n, 4), dtype=torch.float32, device=self.device)
-            self._bcast_action.copy_(action.to(device=self.device, dtype=torch.float32).expand(self.n, 4))
-            action = self._bcast_action
-        if action.shape != (self.n, 4):
-            raise ValueError(f"action must have shape ({self.n}, 4), got {tuple(action.shape)}")
-        if action.dtype in (torch.float16, torch.bfloat16, torch.float64) and action.device == self.state.device:
-            action = self._cast_sticks(action)           # one rule for step(), rollout() and step_async()
-        if action.dtype != torch.float32 or action.device != self.state.device or not action.is_contiguous():
-            action = action.to(device=self.device, dtype=torch.float32).contiguous()
-        return action
-
-    _warned_cast = False
-
-    def _cast_sticks(self, action: torch.Tensor) -> torch.Tensor:
-        """A stick tensor of another floating dtype as contiguous float32 (one cast kernel per call; warned about once: a
-        half-precision policy that cares writes `.float()` into a preallocated buffer itself).  The same rule in step(),
-        rollout() and step_async()."""
-        if not _Batch._warned_cast:
-            import warnings
-            warnings.warn(f"sticks of dtype {action.dtype} are cast to float32 on every call (the kernels read float32 sticks since ABI 6)",
-                          RuntimeWarning, stacklevel=3)
-            _Batch._warned_cast = True
-        return action.to(torch.float32).contiguous()
-
-    def set_step_counter(self, step: int) -> None:
-        """64-bit step index keying the stick-noise stream / stochastic rounding (counts the steps launched, from 0)."""
-        if not 0 <= int(step) < 2 ** 64:
-            raise ValueError("the step counter is an unsigned 64-bit integer")
-        _lib.check(self._L.fpv_set_step_counter(self._handle, int(step)))
-        self._steps_launched = int(step)
 
     def step_counter(self) -> int:
         """The handle's own 64-bit step counter (fpv_get_step_counter)."""
@@ -284,12 +355,6 @@ class _Batch:
         _lib.check(self._L.fpv_get_cache_model(self._handle, C.byref(m)))
         return m.as_dict()
 
-    def set_params(self, params: DroneParams, auto_reset: Optional[bool] = None) -> None:
-        flags_auto = bool(self._cparams.flags & _lib.FPV_FLAG_AUTO_RESET) if auto_reset is None else auto_reset
-        cp = _lib.pack_params(params, auto_reset=flags_auto, **self._pack_kw)
-        _lib.check(self._L.fpv_set_params(self._handle, C.byref(cp)))
-        self.params, self._cparams = params, cp
-
     # -- checkpoint / resume (the reference has none; state is just tensors here) ------------------
     _CKPT_TENSORS = ("state", "state_h", "reward", "done", "ep_return", "ep_length", "last_return",
                      "last_length", "noise_state", "pos_comp", "reset_pose")
@@ -316,8 +381,7 @@ class _Batch:
             if k in self._CKPT_ROW_TENSORS:
                 d[k] = t[:, :self.n].clone()
             elif k == "state_h":
-                pairs, thrust = self._state_h_views()
-                d[k] = torch.cat([pairs[:, :self.n].permute(0, 2, 1).reshape(-1, self.n), thrust[:self.n].view(1, self.n)], dim=0)
+                d[k] = self._storage_words(self.n)
             else:
                 d[k] = t.clone()
         d["step_counter"] = int(self._steps_launched)
@@ -385,17 +449,6 @@ class _Batch:
                 mine.copy_(src)
         self.set_step_counter(d["step_counter"])
 
-    def close(self) -> None:
-        if getattr(self, "_handle", None) is not None and self._handle.value:
-            self._L.fpv_destroy(self._handle)
-            self._handle = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
     # -- raw stepping -----------------------------------------------------------------------------
     def _reset_raw(self, mask=None, position=None, velocity=None, ypr=None) -> None:
         def dev3(x):
@@ -439,16 +492,6 @@ class _Batch:
         else:
             self._objects = None
             self._buf.objects = None
-
-    def _step_raw(self, action: Any, wind: Optional[Sequence[float]] = None) -> None:
-        b = self._buf
-        b.action = self._action_ptr(action)
-        if wind is not None:
-            b.wind[0], b.wind[1], b.wind[2] = float(wind[0]), float(wind[1]), float(wind[2])
-        rc = self._fpv_step(self._handle, self._buf_ref, self._stream())
-        if rc < 0:
-            _lib.check(rc)
-        self._steps_launched = (self._steps_launched + 1) & 0xFFFFFFFFFFFFFFFF
 
     def set_done_bits_target(self, target: Any = None, stride_words: int = 0) -> None:
         """Where the kernel writes the bit-packed done mask (one wave ballot per 64 drones):
@@ -502,16 +545,9 @@ class _Batch:
             if rewards is None and dones is None and steps is None:
                 raise ValueError("held-action rollouts need rewards/dones [k, num_envs] or steps=k to define k")
             k, stride = (int(steps) if steps is not None else (rewards if rewards is not None else dones).shape[0]), 0
-        if actions is not None and actions.dtype in (torch.float16, torch.bfloat16, torch.float64) and actions.device == self.state.device:
-            actions = self._cast_sticks(actions)           # as step() does: the kernels read float32 sticks (ABI 6 dropped the binary16 rows)
-        if actions is not None and (actions.dtype != torch.float32 or not actions.is_contiguous()
-                                    or actions.device != self.state.device):
-            raise ValueError("actions must be a contiguous float32 tensor on the env's device (float16 / bfloat16 / float64 "
-                             "tensors there are cast once per call)")
-        b.action = actions.data_ptr() if actions is not None else None
-        b.action_ld = 0
+        actions, b.action, b.action_ld = self._sticks(actions, block=True)
         if wind is not None:
-            b.wind[0], b.wind[1], b.wind[2] = float(wind[0]), float(wind[1]), float(wind[2])
+            _set_wind(b, wind)
         out_stride = 0
         saved = (b.reward, b.done)
         if rewards is not None or dones is not None:
@@ -536,7 +572,6 @@ class _Batch:
             _lib.check(fn(self._handle, C.byref(b), int(k), stride, out_stride, self._stream()))
             self._steps_launched = (self._steps_launched + int(k)) & 0xFFFFFFFFFFFFFFFF
             self._keepalive = actions               # what `throttle` reports: the last step's sticks
-            self._last_action = None                # the next step() re-validates its tensor (b.action / action_ld were rewritten here)
         finally:
             b.reward, b.done = saved
 
@@ -561,36 +596,37 @@ class _Batch:
         state by the return-triple kernel (one launch; the transpose of its R.T output is a view), otherwise by tensor
         operations."""
         if self.mode == MODE_DRONE and not self.fp16_state:
-            rt = torch.empty((self.n, 3, 3), dtype=torch.float32, device=self.device)
-            gy = torch.empty((self.n, 3, 3), dtype=torch.float32, device=self.device)
-            _lib.check(self._L.fpv_return_triple(self._handle, self._buf_ref, rt.data_ptr(), gy.data_ptr(), None, self._stream()))
-            return rt.transpose(-1, -2)
+            return self._return_triple(False)[0].transpose(-1, -2)
         return quat_to_matrix(self.quaternion)
 
+    def _return_triple(self, with_accel: bool):
+        """(R.T [n, 3, 3], gyro [n, 3, 3], accel [n, 3] or None) of fp32 drone state: one launch of fpv_return_triple
+        into fresh tensors (like the reference's fresh arrays: a caller may keep them across steps)."""
+        f32 = dict(dtype=torch.float32, device=self.device)
+        rt, gyro = torch.empty((self.n, 3, 3), **f32), torch.empty((self.n, 3, 3), **f32)
+        acc = torch.empty((self.n, 3), **f32) if with_accel else None
+        _lib.check(self._L.fpv_return_triple(self._handle, self._buf_ref, rt.data_ptr(), gyro.data_ptr(),
+                                             acc.data_ptr() if acc is not None else None, self._stream()))
+        return rt, gyro, acc
 
-class _Partition:
+
+class _Partition(_Handle):
     """Columns [lo, hi) of a parent batch as a stepper of their own: the SAME device tensors (every pointer is the
     parent's, moved by `lo` elements; the row stride is the parent's), its own C handle (n = hi - lo drones, global
     ids continuing the parent's: `drone_id_offset + lo`), its own stream.  A partition's steps form an independent
     chain of kernels; chains of different partitions overlap on the GPU, which hides a part of each other's per-launch
-    floor.  `lo` is a multiple of 128 - whole workgroups, whole done-mask words, 16-byte aligned rows."""
+    floor.  `lo` is a multiple of 128 - whole workgroups, whole done-mask words, 16-byte aligned rows.
+    It takes its own slice of the sticks only: [n, 4] rows or [4, n] SoA, float32 or cast (`_sticks`)."""
+
+    _coerce = False
 
     def __init__(self, parent: "_Batch", lo: int, hi: int, stream: Optional[torch.cuda.Stream]):
         if lo % 128 or not lo < hi <= parent.n:
             raise ValueError("a partition starts at a multiple of 128 drones and is not empty")
-        self.parent, self.lo, self.hi, self.n = parent, lo, hi, hi - lo
+        self.parent, self.lo, self.hi = parent, lo, hi
         self.stream = stream if stream is not None else torch.cuda.Stream(device=parent.device)
-        self._stream_ptr = self.stream.cuda_stream
-        self._L = parent._L
-        kw = dict(parent._pack_kw, drone_id_offset=int(parent._pack_kw.get("drone_id_offset", 0)) + lo)
-        auto = bool(parent._cparams.flags & _lib.FPV_FLAG_AUTO_RESET)
-        self._cparams = _lib.pack_params(parent.params, auto_reset=auto, **kw)
-        self._handle = C.c_void_p()
-        _lib.check(self._L.fpv_create(C.byref(self._cparams), self.n, parent._dev_index, C.byref(self._handle)))
-        self._buf = _lib.FpvBuffers()
-        self._buf_ref = C.byref(self._buf)
-        self._ashape, self._keep = torch.Size((self.n, 4)), None
-        self.steps_launched = 0
+        super().__init__(parent.params, hi - lo, parent.device, parent._dev_index, parent._auto_reset,
+                         dict(parent._pack_kw, drone_id_offset=int(parent._pack_kw["drone_id_offset"]) + lo))
         self.rebind()
 
     def rebind(self) -> None:
@@ -615,65 +651,6 @@ class _Partition:
         else:
             b.state_h = b.state_h_thrust = None
         b.done_bits_stride = 0
-
-    def action_ptr(self, action: Any) -> Optional[int]:
-        if action is None:
-            if not self.parent.stick_noise:
-                raise ValueError("action=None is only meaningful with stick_noise=True (pure noise sticks)")
-            return None
-        st = self.parent.state
-        if type(action) is torch.Tensor and action.dtype in (torch.float16, torch.bfloat16, torch.float64) and action.device == st.device:
-            # as step() and rollout() do, but on THIS partition's stream, after step_async's wait (ready=True makes none: the
-            # caller has said the input is complete): the float32 copy is written before the step reads it, and it is allocated
-            # from and freed to this stream's pool, so it is not handed out again before the step is through.  The input is read
-            # there too: record_stream keeps the caller's pool from handing it out again before the cast has run.
-            action.record_stream(self.stream)
-            with torch.cuda.stream(self.stream):
-                action = self.parent._cast_sticks(action)
-        if type(action) is torch.Tensor and action.dtype is torch.float32 and action.device == st.device:
-            if action.shape == self._ashape and action.is_contiguous():               # [n_p, 4] rows (a row slice of [N, 4] is one)
-                self._buf.action_ld = 0
-                self._keep = action
-                return action.data_ptr()
-            if (action.dim() == 2 and action.shape[0] == 4 and action.shape[1] == self.n and self.n != 4
-                    and action.stride(1) == 1 and action.stride(0) >= self.n):         # SoA [4, n_p] (a column slice of [4, N] is one)
-                self._buf.action_ld = action.stride(0)
-                self._keep = action
-                return action.data_ptr()
-        raise ValueError(f"a partition's action is a float32 tensor on the env's device, [{self.n}, 4] contiguous rows or "
-                         f"[4, {self.n}] with unit column stride (slices of a full-size tensor qualify)")
-
-    def launch(self, action: Any) -> None:
-        b = self._buf
-        b.action = self.action_ptr(action)
-        rc = self._L.fpv_step(self._handle, self._buf_ref, self._stream_ptr)
-        if rc < 0:
-            _lib.check(rc)
-        self.steps_launched += 1
-
-    def set_step_counter(self, step: int) -> None:
-        _lib.check(self._L.fpv_set_step_counter(self._handle, int(step)))
-        self.steps_launched = int(step)
-
-    def set_params(self) -> None:
-        """Take over the parent's current parameters (FpvVecEnv.set_params), keeping this partition's drone-id offset."""
-        parent = self.parent
-        kw = dict(parent._pack_kw, drone_id_offset=int(parent._pack_kw.get("drone_id_offset", 0)) + self.lo)
-        auto = bool(parent._cparams.flags & _lib.FPV_FLAG_AUTO_RESET)
-        cp = _lib.pack_params(parent.params, auto_reset=auto, **kw)
-        _lib.check(self._L.fpv_set_params(self._handle, C.byref(cp)))
-        self._cparams = cp
-
-    def close(self) -> None:
-        if getattr(self, "_handle", None) is not None and self._handle.value:
-            self._L.fpv_destroy(self._handle)
-            self._handle = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
 
 def partition_bounds(n: int, parts: int) -> Sequence[Tuple[int, int]]:
@@ -829,14 +806,7 @@ class DroneBatch(_Batch):
         if not return_imu:
             return None
         if not self.fp16_state:
-            # one small kernel (fpv_return_triple) instead of ~30 tensor operations: fresh tensors every call, like the
-            # reference's fresh arrays (a caller may keep them across steps)
-            rt = torch.empty((self.n, 3, 3), dtype=torch.float32, device=self.device)
-            gyro = torch.empty((self.n, 3, 3), dtype=torch.float32, device=self.device)
-            acc = torch.empty((self.n, 3), dtype=torch.float32, device=self.device) if self.accel is not None else None
-            _lib.check(self._L.fpv_return_triple(self._handle, self._buf_ref, rt.data_ptr(), gyro.data_ptr(),
-                                                 acc.data_ptr() if acc is not None else None, self._stream()))
-            return rt, gyro, acc
+            return self._return_triple(self.accel is not None)      # one small kernel instead of ~30 tensor operations
         R = self.rotation_matrix
         rates = self.rows_f32(_lib.RX, _lib.RZ + 1)
         gyro = euler_zyx_matrix(rates)            # deg/s values used as radians, as the reference does (:247)
@@ -889,7 +859,7 @@ class DroneBatch(_Batch):
     def throttle(self) -> Optional[torch.Tensor]:
         """[num_envs] throttle stick of the last step (Drone.throttle, components.py:186; simulator.py:161 prints it).
         None before the first step or after a step driven purely by in-kernel stick noise (read `action_out` then)."""
-        a = getattr(self, "_keepalive", None)
+        a = self._keepalive
         if a is None or self._buf.action is None:
             return None
         if a.dim() == 3:                             # a rollout's [k, num_envs, 4] batch: its last step
@@ -971,7 +941,7 @@ class FpvVecEnv:
         self._parts: list = []
         self.stream_report: Optional[Dict[str, Any]] = None
         if int(partitions) > 1:
-            self.batch._buf.wind[0], self.batch._buf.wind[1], self.batch._buf.wind[2] = self.wind
+            _set_wind(self.batch._buf, self.wind)
             bounds = partition_bounds(self.num_envs, int(partitions))
             if len(bounds) > 1:
                 # streams whose kernel chains really overlap - with each other and with the caller's stream (where a policy
@@ -1030,28 +1000,33 @@ class FpvVecEnv:
         cur = self._caller_waits_for_partitions()      # steps still in flight on the partitions' streams finish first
         if self.batch._cparams.flags & _lib.FPV_FLAG_RESET_JITTER:
             # the jitter of an explicit reset is keyed by the step counter: the partitions', which stepped this population
-            self.batch.set_step_counter(min(P.steps_launched for P in self._parts))
+            self.batch.set_step_counter(min(P._steps_launched for P in self._parts))
         self.batch.reset(mask=mask, **kw)              # (the step counters run on, as the unpartitioned batch's does across a reset)
         self._partitions_wait_for(cur)
         return self.obs
 
     def step(self, action) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor, Dict[str, Any]]:
         if self._parts:
-            soa = False
-            if action is not None:
-                soa = (type(action) is torch.Tensor and action.dim() == 2 and action.shape[0] == 4 and action.shape[1] == self.num_envs != 4
-                       and action.dtype is torch.float32 and action.stride(1) == 1 and action.device == self.batch.state.device)
-                if not soa:
-                    action = self.batch._coerce_action(action)       # lists, arrays, [4] broadcasts, other dtypes: as the single batch takes them
+            # lists, arrays, [4] broadcasts, other dtypes: as the single batch takes them, on the caller's stream; then each
+            # partition's slice of the rows or of the SoA columns
+            a, _, soa = self.batch._sticks(action)
             for k, P in enumerate(self._parts):
-                self.step_async(k, None if action is None else action[:, P.lo:P.hi] if soa else action[P.lo:P.hi])
+                self.step_async(k, None if a is None else a[:, P.lo:P.hi] if soa else a[P.lo:P.hi])
             for k in range(len(self._parts)):
                 self.step_wait(k)
             return self.obs, self.batch.reward, self.batch.done, self._info(self.batch, 0, self.num_envs)
-        if self.object_list or self.batch._buf.objects:
-            self.batch._set_objects(self.object_list)
-        self.batch._step_raw(action, self.wind)
+        self._bind_world(self.batch)
+        self.batch._step_raw(action)
         return self.obs, self.batch.reward, self.batch.done, self._info(self.batch, 0, self.num_envs)
+
+    def _bind_world(self, stepper: _Handle) -> None:
+        """The env's collision world and wind into the buffers of `stepper` (the batch, or a partition: the batch packs the
+        table), on every step, like the reference passes them to every Drone.step."""
+        b = self.batch
+        if self.object_list or b._buf.objects:
+            b._set_objects(self.object_list)
+            stepper._buf.objects = b._buf.objects
+        _set_wind(stepper._buf, self.wind)
 
     @staticmethod
     def _info(batch, lo: int, hi: int) -> Dict[str, Any]:
@@ -1093,12 +1068,8 @@ class FpvVecEnv:
             cur = torch.cuda.current_stream(self.batch.device)
             if cur != P.stream:
                 P.stream.wait_stream(cur)
-        if self.object_list or self.batch._buf.objects:
-            self.batch._set_objects(self.object_list)
-            P._buf.objects = self.batch._buf.objects
-        w = self.wind                                   # read on every step, like the single batch's step(action, self.wind)
-        P._buf.wind[0], P._buf.wind[1], P._buf.wind[2] = w[0], w[1], w[2]
-        P.launch(action)
+        self._bind_world(P)
+        P._step_raw(action, stream=P.stream)
 
     def step_wait(self, part: int, sync: bool = True) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor, Dict[str, Any]]:
         """(obs, reward, done, info) of partition `part` - views of its columns - ordered after its last enqueued step:
@@ -1112,8 +1083,7 @@ class FpvVecEnv:
         b = self.batch
         if b.fp16_state:
             # fp16 storage: a decoded copy of this partition's columns (one launch of fpv_widen_state on ITS handle), fresh every time
-            wide = torch.empty((_lib.FPV_DRONE_ROWS, _round_up(P.n, 64)), dtype=torch.float32, device=b.device)
-            _lib.check(b._L.fpv_widen_state(P._handle, P._buf_ref, wide.data_ptr(), wide.shape[1], b._stream()))
+            wide = P._widen(_round_up(P.n, 64))
             return wide[:13, :P.n].t(), b.reward[P.lo:P.hi], b.done[P.lo:P.hi], self._info(b, P.lo, P.hi)
         v = self._part_views[part]
         if v is None:
@@ -1136,7 +1106,7 @@ class FpvVecEnv:
         enqueued keep the ones they were launched with, exactly as on the single batch."""
         self.batch.set_params(params, auto_reset)
         for P in self._parts:
-            P.set_params()
+            P.set_params(params, self.batch._auto_reset)
 
     def state_dict(self) -> Dict[str, Any]:
         """The batch's checkpoint; with partitions the step counters of all of them (they key the stick-noise streams).
@@ -1144,7 +1114,7 @@ class FpvVecEnv:
         self._caller_waits_for_partitions()
         d = self.batch.state_dict()
         if self._parts:
-            d["partition_step_counters"] = [P.steps_launched for P in self._parts]
+            d["partition_step_counters"] = [P._steps_launched for P in self._parts]
             d["step_counter"] = min(d["partition_step_counters"])        # what an unpartitioned env continues from
         return d
 

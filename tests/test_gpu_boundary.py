@@ -679,7 +679,7 @@ def test_reference_scalar_attributes_of_drone(params_1k):
     acts = torch.rand((5, 7, 4), device=DEV) * 2 - 1
     env.rollout(acts)
     assert torch.equal(env.throttle, acts[-1, :, 3])
-    # step(A); rollout(...); step(A) with the SAME tensor object: the in-place-policy fast path of _action_ptr must report A
+    # step(A); rollout(...); step(A) with the SAME tensor object: the in-place-policy fast path of the stick intake (_sticks) must report A
     # again (it used to leave `throttle` on the rollout's batch), and a tensor re-shaped in place is validated again
     env.step(a, return_imu=False)
     env.rollout(acts)
