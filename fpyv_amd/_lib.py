@@ -23,6 +23,9 @@ FPV_FLAG_FP16_STATE = 4
 FPV_FLAG_STICK_NOISE = 8
 FPV_FLAG_RESET_JITTER = 16
 RESET_POSE_ROWS = 10          # fpv_buffers_t.reset_pose: [10][ld] = p3 v3 q4 (wxyz), the state's row order
+FPV_PHYS_ROWS = 13            # fpv_set_physics: [13][ld] derived constants per drone (fpv_abi.h FPV_PHYS_*)
+FPV_PHYS_INPUTS = 10          # a parameter set: mass, c3 c2 c1 c0, Cd x y z, rates_transition_rate, thrust_transition_rate
+PHYS_IN_MASS, PHYS_IN_C3, PHYS_IN_CD_X, PHYS_IN_RATES_LAG, PHYS_IN_THRUST_LAG = 0, 1, 5, 8, 9
 FPV_HALF_PAIR_ROWS = 5
 FPV_HALF_HALVES = 11          # binary16 values per drone in state_h (5 pair rows + 1 half row)
 FPV_OBS_AOS_DIM = 16
@@ -37,7 +40,8 @@ EXPORTS = ("fpv_abi_version", "fpv_sizeof", "fpv_state_rows", "fpv_algorithmic_b
            "fpv_recommended_ld_device", "fpv_check_cache_model", "fpv_device_cache_model", "fpv_get_cache_model",
            "fpv_diag_stream_copy", "fpv_diag_stream_copy_wide", "fpv_diag_busy", "fpv_diag_xcd_map", "fpv_pid_reset", "fpv_pid_call", "fpv_comm_unique_id", "fpv_comm_create", "fpv_comm_destroy", "fpv_comm_info",
            "fpv_allgather_done", "fpv_allgather_f32", "fpv_last_error",
-           "fpv_error_name", "fpv_encoding_id", "fpv_reset_pose_sample")
+           "fpv_error_name", "fpv_encoding_id", "fpv_reset_pose_sample",
+           "fpv_physics_rows", "fpv_physics_derive", "fpv_physics_sample", "fpv_set_physics", "fpv_get_physics")
 
 
 class FpvParams(C.Structure):
@@ -244,6 +248,11 @@ def lib() -> C.CDLL:
     L.fpv_encoding_id.restype = C.c_char_p
     L.fpv_sizeof.argtypes = [C.c_int]
     L.fpv_reset_pose_sample.argtypes = [pp, C.c_uint64, C.c_uint64, C.c_int, vp, vp]
+    L.fpv_physics_rows.restype = C.c_int
+    L.fpv_physics_derive.argtypes = [pp, i64, vp, vp, i64]
+    L.fpv_physics_sample.argtypes = [pp, C.c_uint64, C.c_uint64, i64, vp, vp]
+    L.fpv_set_physics.argtypes = [vp, vp, i64]
+    L.fpv_get_physics.argtypes = [vp, C.POINTER(vp), C.POINTER(i64)]
     if L.fpv_abi_version() != FPV_ABI_VERSION:
         raise ImportError(f"libfpv_hip.so ABI {L.fpv_abi_version()} != binding {FPV_ABI_VERSION} - rebuild the library "
                           "(`python -c 'import __graft_entry__ as g; g.build()'`)")

@@ -16,6 +16,39 @@
 #include "../../include/fpv_abi.h"
 #include "fpv_math.h"
 
+// The per-drone part of the narrowing (include/fpv_abi.h "Per-drone physics"): the FPV_PHYS_ROWS constants of ONE parameter set
+// `in` (FPV_PHYS_INPUTS doubles: mass, c3 c2 c1 c0, Cd x y z, rates_transition_rate, thrust_transition_rate) on the uniform
+// parameters of `P` (max_rates, air density, cross sections, ground spring / damping).  fpv_derive_constants calls it with P's own
+// values, fpv_physics_derive once per drone: a drone's table column IS the constants of a handle built with its parameters.
+static inline void fpv_derive_physics_rows(const fpv_params_t* P, const double in[FPV_PHYS_INPUTS], float row[FPV_PHYS_ROWS])
+{
+    const double mass = in[FPV_PHYS_IN_MASS], kr = in[FPV_PHYS_IN_RATES_LAG], kt = in[FPV_PHYS_IN_THRUST_LAG];
+    const double c3 = in[FPV_PHYS_IN_C3], c2 = in[FPV_PHYS_IN_C2], c1 = in[FPV_PHYS_IN_C1], c0 = in[FPV_PHYS_IN_C0];
+    const double h = 50.0;   // x = h*a + h
+    row[FPV_PHYS_RATE_LIM] = (float)(P->max_rates * kr);
+    row[FPV_PHYS_OMKR] = (float)(1.0 - kr);
+    row[FPV_PHYS_OMKT] = (float)(1.0 - kt);
+    row[FPV_PHYS_DK3] = (float)(kt * (c3 * h * h * h));
+    row[FPV_PHYS_DK2] = (float)(kt * (3 * c3 * h * h * h + c2 * h * h));
+    row[FPV_PHYS_DK1] = (float)(kt * (3 * c3 * h * h * h + 2 * c2 * h * h + c1 * h));
+    row[FPV_PHYS_DK0] = (float)(kt * (c3 * h * h * h + c2 * h * h + c1 * h + c0));
+    for (int i = 0; i < 3; ++i)
+        row[FPV_PHYS_KDRAG_X + i] = (float)(0.5 * in[FPV_PHYS_IN_CD_X + i] * P->air_density * P->cross_section_areas[i] / mass);
+    row[FPV_PHYS_INV_MASS] = (float)(1.0 / mass);
+    row[FPV_PHYS_GROUND_K_M] = (float)(P->ground_spring / mass);
+    row[FPV_PHYS_GROUND_C_M] = (float)(P->ground_damping / mass);
+}
+
+// P's own parameter set as the inputs of fpv_derive_physics_rows
+static inline void fpv_physics_base_inputs(const fpv_params_t* P, double in[FPV_PHYS_INPUTS])
+{
+    in[FPV_PHYS_IN_MASS] = P->mass;
+    for (int i = 0; i < 4; ++i) in[FPV_PHYS_IN_C3 + i] = P->thrust_poly[i];
+    for (int i = 0; i < 3; ++i) in[FPV_PHYS_IN_CD_X + i] = P->drag_coefficients[i];
+    in[FPV_PHYS_IN_RATES_LAG] = P->rates_transition_rate;
+    in[FPV_PHYS_IN_THRUST_LAG] = P->thrust_transition_rate;
+}
+
 // Returns 0 or an FPV_E* code; *why receives a static message on failure.
 static inline int fpv_derive_constants(const fpv_params_t* P, FpvK* K, const char** why)
 {
@@ -48,28 +81,27 @@ static inline int fpv_derive_constants(const fpv_params_t* P, FpvK* K, const cha
     K->dt = (float)P->dt;
     K->max_rates = (float)P->max_rates;
     K->kr = (float)P->rates_transition_rate;
-    K->omkr = (float)(1.0 - P->rates_transition_rate);
     K->kt = (float)P->thrust_transition_rate;
-    K->omkt = (float)(1.0 - P->thrust_transition_rate);
     const double c3 = P->thrust_poly[0], c2 = P->thrust_poly[1], c1 = P->thrust_poly[2], c0 = P->thrust_poly[3];
     const double h = 50.0;   // x = h*a + h
     K->d3 = (float)(c3 * h * h * h);
     K->d2 = (float)(3 * c3 * h * h * h + c2 * h * h);
     K->d1 = (float)(3 * c3 * h * h * h + 2 * c2 * h * h + c1 * h);
     K->d0 = (float)(c3 * h * h * h + c2 * h * h + c1 * h + c0);
-    {
-        const double kt = P->thrust_transition_rate;
-        K->dk3 = (float)(kt * (c3 * h * h * h));
-        K->dk2 = (float)(kt * (3 * c3 * h * h * h + c2 * h * h));
-        K->dk1 = (float)(kt * (3 * c3 * h * h * h + 2 * c2 * h * h + c1 * h));
-        K->dk0 = (float)(kt * (c3 * h * h * h + c2 * h * h + c1 * h + c0));
-        K->rate_lim = (float)(P->max_rates * P->rates_transition_rate);
+    {   // everything a physics table can replace per drone, by the function that fills the table
+        double in[FPV_PHYS_INPUTS];
+        float row[FPV_PHYS_ROWS];
+        fpv_physics_base_inputs(P, in);
+        fpv_derive_physics_rows(P, in, row);
+        K->rate_lim = row[FPV_PHYS_RATE_LIM];
         K->rate_gain = -K->rate_lim;
+        K->omkr = row[FPV_PHYS_OMKR]; K->omkt = row[FPV_PHYS_OMKT];
+        K->dk3 = row[FPV_PHYS_DK3]; K->dk2 = row[FPV_PHYS_DK2]; K->dk1 = row[FPV_PHYS_DK1]; K->dk0 = row[FPV_PHYS_DK0];
+        for (int i = 0; i < 3; ++i) K->kdrag_m[i] = row[FPV_PHYS_KDRAG_X + i];
+        K->inv_mass = row[FPV_PHYS_INV_MASS];
+        K->ground_k_m = row[FPV_PHYS_GROUND_K_M]; K->ground_c_m = row[FPV_PHYS_GROUND_C_M];
     }
-    K->inv_mass = (float)(1.0 / P->mass);
     K->g = (float)P->gravity;
-    for (int i = 0; i < 3; ++i)
-        K->kdrag_m[i] = (float)(0.5 * P->drag_coefficients[i] * P->air_density * P->cross_section_areas[i] / P->mass);
     K->half_k = (float)(0.5 * (M_PI / 180.0) * P->dt);
     for (int m = 0; m < 4; ++m) { K->motor_x[m] = (float)P->motor_xy[m][0]; K->motor_y[m] = (float)P->motor_xy[m][1]; }
     {   // the reference's X frame after narrowing: (c,c) (-c,c) (-c,-c) (c,-c) in any order, one |c| bit for bit
@@ -113,8 +145,6 @@ static inline int fpv_derive_constants(const fpv_params_t* P, FpvK* K, const cha
     K->rf.integral_clip = (float)K->rd.integral_clip; K->rf.min_output = (float)K->rd.min_output;
     K->rf.max_output = (float)K->rd.max_output; K->rf.d_rate = (float)K->rd.d_rate; K->rf.om_d_rate = (float)K->rd.om_d_rate;
     K->motor_radius = (float)P->motor_radius;
-    K->ground_k_m = (float)(P->ground_spring / P->mass);
-    K->ground_c_m = (float)(P->ground_damping / P->mass);
     double arm = 0.0;
     for (int m = 0; m < 4; ++m) arm = fmax(arm, sqrt(P->motor_xy[m][0] * P->motor_xy[m][0] + P->motor_xy[m][1] * P->motor_xy[m][1]));
     K->contact_reach = (float)(arm + fmax(P->motor_radius, 0.0) + 1e-3);
@@ -150,4 +180,51 @@ static inline int fpv_derive_reset_jitter(const fpv_params_t* P, FpvResetJitter*
         }
     J->seed_lo = (uint32_t)P->reset_seed; J->seed_hi = (uint32_t)(P->reset_seed >> 32);
     return FPV_OK;
+}
+
+// fpv_physics_derive (include/fpv_abi.h): the table columns of n parameter sets.  A NaN cell takes the base value.  Returns 0, or
+// FPV_EPARAM with *bad = the first drone whose mass is not positive or that has an infinite cell.
+static inline int fpv_derive_physics_table(const fpv_params_t* P, int64_t n, const double* inputs, float* out_rows, int64_t out_ld,
+                                           int64_t* bad, const char** why)
+{
+    double base[FPV_PHYS_INPUTS];
+    fpv_physics_base_inputs(P, base);
+    for (int64_t i = 0; i < n; ++i) {
+        double in[FPV_PHYS_INPUTS];
+        float row[FPV_PHYS_ROWS];
+        for (int c = 0; c < FPV_PHYS_INPUTS; ++c) {
+            const double v = inputs ? inputs[i * FPV_PHYS_INPUTS + c] : base[c];
+            in[c] = isnan(v) ? base[c] : v;
+            if (isinf(in[c])) { *bad = i; *why = "a physics input is not finite"; return FPV_EPARAM; }
+        }
+        if (!(in[FPV_PHYS_IN_MASS] > 0)) { *bad = i; *why = "mass must be positive"; return FPV_EPARAM; }
+        fpv_derive_physics_rows(P, in, row);
+        for (int r = 0; r < FPV_PHYS_ROWS; ++r) out_rows[(int64_t)r * out_ld + i] = row[r];
+    }
+    return FPV_OK;
+}
+
+// fpv_physics_sample (include/fpv_abi.h): relative factors lo + (hi - lo) u on the base values, u = (w >> 8) * 2^-24 of a
+// Philox4x32-7 word; key = seed, counter = (gid lo, gid hi ^ (block << 28), FPV_PHYS_SAMPLE_TAG, 0).  Block 0: words 0..3 = mass,
+// motor strength (all four thrust coefficients; the range of the c3 column), rates lag, thrust lag; block 1: words 0..2 = Cd x y z.
+#define FPV_PHYS_SAMPLE_TAG 0x53594850u      /* "PHYS" */
+static inline void fpv_sample_physics_inputs(const fpv_params_t* P, uint64_t seed, uint64_t gid0, int64_t n, const double* ranges,
+                                             double* out)
+{
+    double base[FPV_PHYS_INPUTS];
+    fpv_physics_base_inputs(P, base);
+    for (int64_t i = 0; i < n; ++i) {
+        const uint64_t gid = gid0 + (uint64_t)i;
+        uint32_t w0[4], w1[4];
+        fpv_philox4x32<FPV_NOISE_PHILOX_ROUNDS>((uint32_t)gid, (uint32_t)(gid >> 32), FPV_PHYS_SAMPLE_TAG, 0u, (uint32_t)seed, (uint32_t)(seed >> 32), w0);
+        fpv_philox4x32<FPV_NOISE_PHILOX_ROUNDS>((uint32_t)gid, (uint32_t)(gid >> 32) ^ (1u << 28), FPV_PHYS_SAMPLE_TAG, 0u, (uint32_t)seed, (uint32_t)(seed >> 32), w1);
+        double f[FPV_PHYS_INPUTS];
+        const uint32_t word[FPV_PHYS_INPUTS] = {w0[0], w0[1], w0[1], w0[1], w0[1], w1[0], w1[1], w1[2], w0[2], w0[3]};
+        for (int c = 0; c < FPV_PHYS_INPUTS; ++c) {
+            const int rc = (c >= FPV_PHYS_IN_C3 && c <= FPV_PHYS_IN_C0) ? FPV_PHYS_IN_C3 : c;      // one factor for the whole cubic
+            const double lo = ranges[2 * rc], hi = ranges[2 * rc + 1];
+            f[c] = lo + (hi - lo) * ((double)(word[c] >> 8) * 0x1p-24);
+            out[i * FPV_PHYS_INPUTS + c] = base[c] * f[c];
+        }
+    }
 }

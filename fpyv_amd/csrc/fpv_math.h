@@ -607,7 +607,10 @@ static inline void fpv_objects_bounds(FpvObjects& T, float reach)
 // that a wave takes only when one of its drones is near that object (same expressions, same bits as forming them
 // up front): on the culled fast path the kernel keeps the register budget of the plain step kernel (round 2 formed
 // them before the object loop: 102 VGPRs, 4 waves per SIMD, even when every object was culled).
-FPV_HD bool fpv_collide_objects(const FpvK& K, const FpvObjects& T, const FpvRot& R, float cx, float cy, float cz,
+// KT: where the constants come from - FpvK (uniform, the kernel argument) or a per-lane struct with the same field names
+// (per-drone physics, csrc/fpv_phys.hip): the same operations on the same values either way.
+template <class KT = FpvK>
+FPV_HD bool fpv_collide_objects(const KT& K, const FpvObjects& T, const FpvRot& R, float cx, float cy, float cz,
                                 float vx, float vy, float vz, float acc[3])
 {
     bool crashed = false;
@@ -704,8 +707,9 @@ FPV_HD bool fpv_collide_objects(const FpvK& K, const FpvObjects& T, const FpvRot
 // same flag.  The single-step kernels are HBM-bound and keep the four-height form (SQ = false): there the extra
 // uniform test costs more than the 14 instructions it saves.
 // NORM = false: no renormalisation of the advanced quaternion (fp16-storage kernels only, see fpv_quat_advance).
-template <bool OBJ = false, bool OUT = true, bool SQ = false, bool NORM = true>
-FPV_HD FpvStepOut fpv_drone_step_lane(const FpvK& K, FpvDroneState& s, float a0, float a1, float a2, float a3,
+// KT: FpvK, or a per-lane struct with the same field names (see fpv_collide_objects).
+template <bool OBJ = false, bool OUT = true, bool SQ = false, bool NORM = true, class KT = FpvK>
+FPV_HD FpvStepOut fpv_drone_step_lane(const KT& K, FpvDroneState& s, float a0, float a1, float a2, float a3,
                                       float wx, float wy, float wz, const FpvObjects* objs = nullptr,
                                       float* kahan = nullptr, const float* rot_over = nullptr, float thrust_over = 0.0f)
 {

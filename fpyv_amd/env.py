@@ -214,7 +214,8 @@ class _Batch(_Handle):
                  track_episodes: bool = False, with_accel: bool = False, with_done_bits: bool = False,
                  fp16_state: bool = False, rounding_seed: int = 0, with_obs_aos: bool = False,
                  stick_noise: bool = False, noise_seed: int = 0, drone_id_offset: int = 0,
-                 with_action_out: bool = False, kahan_position: bool = False, per_drone_reset_pose: bool = False):
+                 with_action_out: bool = False, kahan_position: bool = False, per_drone_reset_pose: bool = False,
+                 per_drone_physics: bool = False):
         if num_envs <= 0:
             raise ValueError("num_envs must be positive")
         device = torch.device(device)
@@ -271,6 +272,16 @@ class _Batch(_Handle):
                 raise ValueError("per_drone_reset_pose is a drone-mode option (the Racer resets to its zero state)")
             self.reset_pose = torch.empty((_lib.RESET_POSE_ROWS, self.ld), **f32)
             self.reset_pose.copy_(torch.from_numpy(self._init_pose()).view(-1, 1).expand(_lib.RESET_POSE_ROWS, self.ld))
+        # per-drone physics (fpv_set_physics): [13, ld] derived constants per drone, read-only for the kernels; initialised from the
+        # base parameters (until set_physics / randomize_physics is called every drone flies the handle's airframe, bit for bit)
+        self.physics = None
+        if per_drone_physics:
+            from . import physics as _physics
+            self.physics = torch.zeros((_lib.FPV_PHYS_ROWS, self.ld), **f32)
+            self.physics[:, :self.n].copy_(torch.from_numpy(_physics.derive(self._cparams, None, 1)).expand(-1, self.n))
+            # (the library refuses the table on a Racer or fp16-state handle here, and with Kahan rows, the guidance override or
+            # the AoS head at the launch that combines them - each by name)
+            _lib.check(self._L.fpv_set_physics(self._handle, self.physics.data_ptr(), self.ld))
         self._objects = None            # the bound fpv_objects_t (None = no collision world bound)
         self._object_rows = None
         self._override_keep = None
@@ -357,8 +368,8 @@ class _Batch(_Handle):
 
     # -- checkpoint / resume (the reference has none; state is just tensors here) ------------------
     _CKPT_TENSORS = ("state", "state_h", "reward", "done", "ep_return", "ep_length", "last_return",
-                     "last_length", "noise_state", "pos_comp", "reset_pose")
-    _CKPT_ROW_TENSORS = ("state", "noise_state", "pos_comp", "reset_pose")        # [rows, ld]: stored as their logical columns [rows, num_envs]
+                     "last_length", "noise_state", "pos_comp", "reset_pose", "physics")
+    _CKPT_ROW_TENSORS = ("state", "noise_state", "pos_comp", "reset_pose", "physics")        # [rows, ld]: stored as their logical columns [rows, num_envs]
 
     def _state_h_views(self, t: Optional[torch.Tensor] = None, ld: Optional[int] = None):
         """(pair rows [5, ld, 2], thrust row [ld]) int16 views of an fp16 storage tensor laid out with row stride `ld`"""
@@ -467,6 +478,43 @@ class _Batch(_Handle):
         _lib.check(self._L.fpv_reset(self._handle, C.byref(self._buf), ptr(m), ptr(pos), ptr(vel), ptr(ang),
                                      self._stream()))
         self._keepalive_reset = (pos, vel, ang, m)
+
+    # -- per-drone physics ------------------------------------------------------------------------
+    def _upload_physics(self, rows: np.ndarray, mask) -> None:
+        """[13, n] float32 table columns into `physics`, the masked columns only, on torch's current stream (ordered like reset)"""
+        if self.physics is None:
+            raise ValueError("this batch was built without per_drone_physics=True")
+        t = torch.from_numpy(rows).to(self.device)
+        mine = self.physics[:, :self.n]
+        if mask is None:
+            mine.copy_(t)
+            return
+        m = torch.as_tensor(mask, device=self.device).to(torch.bool)
+        if m.shape != (self.n,):
+            raise ValueError("mask must have shape (num_envs,)")
+        mine.copy_(torch.where(m.view(1, -1), t, mine))
+
+    def set_physics(self, mass=None, thrust_scale=None, thrust_poly=None, drag_coefficients=None, rates_transition_rate=None,
+                    thrust_transition_rate=None, mask=None) -> None:
+        """The airframe of every drone of `mask` (None = all): each argument None (the base parameters' value), a scalar, [n], or -
+        thrust_poly [4] / [n, 4], drag_coefficients [3] / [n, 3] - a row per drone; `thrust_scale` multiplies the thrust cubic.
+        A call defines the whole parameter set of its drones (an argument left at None goes back to the base value).  The table
+        columns come from fpv_physics_derive - the function that narrows a handle's own constants - and are uploaded on the current
+        stream: steps enqueued afterwards see them.  max_rates, dt and the motor geometry stay the handle's (set_params)."""
+        from . import physics as _physics
+        sets = _physics.inputs(self._cparams, self.n, mass, thrust_scale, thrust_poly, drag_coefficients, rates_transition_rate,
+                               thrust_transition_rate)
+        self._upload_physics(_physics.derive(self._cparams, sets), mask)
+
+    def randomize_physics(self, seed: int, mass=(1.0, 1.0), thrust=(1.0, 1.0), drag=(1.0, 1.0), rates_lag=(1.0, 1.0),
+                          thrust_lag=(1.0, 1.0), mask=None) -> None:
+        """Domain randomisation: every drone of `mask` gets the base parameters times factors drawn uniformly from the (lo, hi)
+        ranges - mass, motor strength (the whole thrust cubic), drag (a factor per axis), the two low-pass rates - by
+        fpv_physics_sample, keyed by `seed` and the drone's GLOBAL id (drone_id_offset + column): the same airframe whatever
+        shard or partition the drone lives in."""
+        from . import physics as _physics
+        sets = _physics.sample(self._cparams, seed, int(self._pack_kw["drone_id_offset"]), self.n, mass, thrust, drag, rates_lag, thrust_lag)
+        self._upload_physics(_physics.derive(self._cparams, sets), mask)
 
     def set_objects(self, object_list) -> None:
         """The collision world of the following `rollout` calls: the same `object_list` a `step` takes, bound until it
@@ -651,6 +699,8 @@ class _Partition(_Handle):
         else:
             b.state_h = b.state_h_thrust = None
         b.done_bits_stride = 0
+        if self.parent.physics is not None:            # this partition's column range of the one table
+            _lib.check(self._L.fpv_set_physics(self._handle, self.parent.physics.data_ptr() + 4 * lo, pb.ld))
 
 
 def partition_bounds(n: int, parts: int) -> Sequence[Tuple[int, int]]:
@@ -921,7 +971,7 @@ class FpvVecEnv:
                  mode: str = "drone", auto_reset: bool = True, track_episodes: bool = True,
                  wind: Sequence[float] = (0.0, 0.0, 0.0), object_list=(), partitions: int = 1, **batch_options: Any):
         """`batch_options` go to DroneBatch / RacerBatch (stick_noise=, noise_seed=, drone_id_offset=,
-        fp16_state=, with_obs_aos=, kahan_position=, with_done_bits=, ...); `object_list` is the
+        fp16_state=, with_obs_aos=, kahan_position=, with_done_bits=, per_drone_physics=, ...); `object_list` is the
         collision world of every step (fpyv_amd.objects); `partitions` > 1 enables step_async / step_wait."""
         if mode not in ("drone", "racer"):
             raise ValueError(f'mode must be "drone" or "racer", got {mode!r}')
@@ -1004,6 +1054,22 @@ class FpvVecEnv:
         self.batch.reset(mask=mask, **kw)              # (the step counters run on, as the unpartitioned batch's does across a reset)
         self._partitions_wait_for(cur)
         return self.obs
+
+    def set_physics(self, **kw) -> None:
+        """DroneBatch.set_physics for the whole population (per_drone_physics=True), ordered after steps in flight like reset."""
+        self._whole_population(self.batch.set_physics, **kw)
+
+    def randomize_physics(self, seed: int, **kw) -> None:
+        """DroneBatch.randomize_physics for the whole population, ordered after steps in flight like reset."""
+        self._whole_population(self.batch.randomize_physics, seed, **kw)
+
+    def _whole_population(self, fn, *a, **kw) -> None:
+        if not self._parts:
+            fn(*a, **kw)
+            return
+        cur = self._caller_waits_for_partitions()
+        fn(*a, **kw)
+        self._partitions_wait_for(cur)
 
     def step(self, action) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor, Dict[str, Any]]:
         if self._parts:

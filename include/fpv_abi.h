@@ -260,6 +260,56 @@ typedef struct fpv_buffers {
 int fpv_reset_pose_sample(const fpv_params_t* params, uint64_t global_id, uint64_t step, int explicit_reset,
                           const float base[10], float out[10]);
 
+/* Per-drone physics (drone mode, fp32 state; functions only - FPV_ABI_VERSION and both structs are those of ABI 9).
+ * A handle may be given a read-only PHYSICS TABLE phys[FPV_PHYS_ROWS][ld]: fp32, the state's row stride and column order, in a
+ * device buffer the caller owns and keeps alive.  Column i holds the DERIVED constants of drone i - exactly the fp32 values
+ * fpv_create narrows from a parameter set with that drone's mass, thrust cubic, drag coefficients and low-pass rates
+ * (csrc/fpv_derive.h fpv_derive_physics_rows: one function fills a handle's constants and a table column), so a drone of a table
+ * handle flies bit for bit like a drone of a homogeneous handle with its parameters.  Rows: */
+enum {
+    FPV_PHYS_RATE_LIM = 0,               /* max_rates * rates_transition_rate (the rate gain is its negation)           */
+    FPV_PHYS_OMKR, FPV_PHYS_OMKT,        /* 1 - rates_transition_rate, 1 - thrust_transition_rate                       */
+    FPV_PHYS_DK3, FPV_PHYS_DK2, FPV_PHYS_DK1, FPV_PHYS_DK0,   /* thrust cubic in the stick, times thrust_transition_rate  */
+    FPV_PHYS_KDRAG_X, FPV_PHYS_KDRAG_Y, FPV_PHYS_KDRAG_Z,     /* 0.5 rho Cd_i A_i / m                                     */
+    FPV_PHYS_INV_MASS,                   /* 1 / m                                                                       */
+    FPV_PHYS_GROUND_K_M, FPV_PHYS_GROUND_C_M,                 /* ground_spring / m, ground_damping / m: loaded only by launches
+                                            that can use them (FPV_FLAG_GROUND or an object list)                      */
+    FPV_PHYS_ROWS                        /* = 13 */
+};
+/* Columns of a parameter set as fpv_physics_derive reads and fpv_physics_sample writes it */
+enum {
+    FPV_PHYS_IN_MASS = 0,                /* kg */
+    FPV_PHYS_IN_C3, FPV_PHYS_IN_C2, FPV_PHYS_IN_C1, FPV_PHYS_IN_C0,      /* thrust_poly */
+    FPV_PHYS_IN_CD_X, FPV_PHYS_IN_CD_Y, FPV_PHYS_IN_CD_Z,                /* drag_coefficients */
+    FPV_PHYS_IN_RATES_LAG, FPV_PHYS_IN_THRUST_LAG,                       /* rates_transition_rate, thrust_transition_rate */
+    FPV_PHYS_INPUTS                      /* = 10 */
+};
+/* Everything else stays uniform and comes from the handle's parameters: dt, gravity, max_rates, the motor geometry, air density
+ * and cross sections, the ground spring and damping (divided by the drone's mass), init pose, noise and flags.  max_rates is
+ * deliberately NOT per drone: it selects the wave-uniform form of the sin / cos of a step (angle_mode), and the default at
+ * fps = 60 sits on a boundary of that choice.  The rows do not depend on dt: a table outlives fpv_set_params(dt), and
+ * fpv_set_params leaves a bound table in force (re-derive it when max_rates, air density, areas or the ground constants move).
+ * Kernels (csrc/fpv_phys.hip): fpv_step / fpv_rollout / fpv_rollout_graph run a single-step kernel that loads the table rows
+ * with the state rows; fpv_step_n a k-step kernel that loads them once and holds them in registers; stick noise, object lists,
+ * FPV_FLAG_GROUND, auto-reset and both reset sources combine with a table (a handle with a reset source runs its single steps
+ * on the k-step kernel, k = 1, as without a table).  Refused with FPV_EINVAL: fp16 state, Racer mode (fpv_set_physics), Kahan rows
+ * (pos_comp), the guidance override and the AoS head (obs_aos) at the launch that combines them with a table.
+ * fpv_handle_algorithmic_bytes of a handle with a table: 133 + 4 * (rows its launches load) = 177, or 185 with the ground rows. */
+int fpv_physics_rows(void);              /* FPV_PHYS_ROWS */
+/* out_rows[r * out_ld + i] = row r of the parameter set inputs[i * FPV_PHYS_INPUTS ..] on `base` (host arithmetic only, no
+ * device; out_rows is HOST memory, out_ld >= n).  A NaN cell means "the base value"; inputs == NULL: all base.  FPV_EPARAM for a
+ * mass that is not positive or an infinite cell: fpv_last_error() names the first offending drone ("drone <index>: ..."). */
+int fpv_physics_derive(const fpv_params_t* base, int64_t n, const double* inputs /*[n][FPV_PHYS_INPUTS]*/,
+                       float* out_rows /*[rows][out_ld]*/, int64_t out_ld);
+/* Randomised parameter sets for drones global_id0 .. global_id0 + n - 1: out_inputs[i][c] = base value * (lo + (hi - lo) u),
+ * u = (w >> 8) * 2^-24 of a Philox4x32-7 word w; key = seed, counter = (gid lo, gid hi ^ (block << 28), 0x53594850, 0): block 0
+ * words 0..3 = mass, motor strength, rates lag, thrust lag, block 1 words 0..2 = Cd x, y, z.  ONE factor scales all four thrust
+ * coefficients (its range is the c3 row of `ranges`; the c2 c1 c0 rows are not read), one factor each Cd axis.  Keyed by the
+ * global drone id only - the style of the reset jitter -, so a drone's parameters do not depend on its shard or partition.
+ * Host arithmetic only.  FPV_EPARAM for a bound that is not finite. */
+int fpv_physics_sample(const fpv_params_t* base, uint64_t seed, uint64_t global_id0, int64_t n,
+                       const double* ranges /*[FPV_PHYS_INPUTS][2], relative factors lo..hi on the base value*/, double* out_inputs);
+
 typedef struct fpv_env* fpv_handle_t;
 
 int fpv_abi_version(void);
@@ -396,6 +446,14 @@ int fpv_rollout_graph(fpv_handle_t h, const fpv_buffers_t* b, int k, int64_t act
 
 /* Replace the drone type of a live handle (e.g. domain randomisation between episodes). */
 int fpv_set_params(fpv_handle_t h, const fpv_params_t* params);
+
+/* Bind (table != NULL) or unbind (NULL) the physics table of a handle ("Per-drone physics" above): a DEVICE pointer to
+ * [FPV_PHYS_ROWS][ld] fp32, 16-byte aligned, ld >= n and a multiple of 4 (FPV_EALIGN otherwise), the caller's to keep alive and
+ * free to rewrite between launches.  ld must be the row stride of the state the handle is stepped with (checked at the launch).
+ * FPV_EINVAL for an fp16-state or Racer handle, and in a library built without csrc/fpv_phys.hip.  fpv_get_physics reads the
+ * binding back (NULL / 0 = none). */
+int fpv_set_physics(fpv_handle_t h, const float* table, int64_t ld);
+int fpv_get_physics(fpv_handle_t h, const float** table, int64_t* ld);
 
 /* Row stride (in floats) to allocate for n drones.  Up to 2^18 drones: n rounded up to 64, padded so that the stride in
  * bytes is at least 1 KiB past a multiple of 8 KiB (strides at or near a multiple of 8 KiB put all 14

@@ -17,6 +17,8 @@ VARIANTS = {
     "base": [],
     "w4": ["-DFPV_EXP_STEP_WAVES=4"], "w5": ["-DFPV_EXP_STEP_WAVES=5"], "w7": ["-DFPV_EXP_STEP_WAVES=7"], "w8": ["-DFPV_EXP_STEP_WAVES=8"], "w44": ["-DFPV_EXP_STEP_WAVES=4,4"], "w55": ["-DFPV_EXP_STEP_WAVES=5,5"], "w33": ["-DFPV_EXP_STEP_WAVES=3,3"],   # occupancy of the step kernel
     "b64": ["-DFPV_EXP_BLOCK=64"], "b256": ["-DFPV_EXP_BLOCK=256"],       # drones per workgroup (the rotation's block, the XCD's share of a row: 256 B of 2 KiB / 1 KiB of 8 KiB)
+    # table loads of the per-drone physics kernels (csrc/fpv_phys.hip; time with --physics): ordinary / with the streaming hint
+    "tab": ["-DFPV_EXP_PHYS_TABLE_NT=0"], "tabnt": ["-DFPV_EXP_PHYS_TABLE_NT=1"],
     "pre12": ["PRELOAD=12"], "pre16": ["PRELOAD=16"], "pre8": ["PRELOAD=8"],       # kernel-argument dwords preloaded into SGPRs (shipped: 6 = state, ld, action; 12 reaches n_start)
 }
 ap = argparse.ArgumentParser()
@@ -25,19 +27,22 @@ ap.add_argument("--n", type=int, default=1 << 20)
 ap.add_argument("--rounds", type=int, default=8)
 ap.add_argument("--only", nargs="*", default=None)
 ap.add_argument("--rotations", nargs="*", type=int, default=[-1], help="fpv_set_rotation values (drones; -1 automatic, 0 plain order) to time every variant at")
+ap.add_argument("--physics", action="store_true", help="bind a randomised physics table (fpv_set_physics) to every variant's handle")
+ap.add_argument("--out", default=OUT, help="where the variant libraries are built and loaded from")
 ap.add_argument("--states", type=int, default=1, help="time every variant on this many separately allocated state matrices (placement matters beyond the cache)")
 a = ap.parse_args()
 names = [k for k in VARIANTS if not a.only or k in a.only]
+OUT = os.path.abspath(a.out)
 if a.build:
     for k in names:
         os.makedirs(OUT, exist_ok=True)
         out = os.path.join(OUT, f"libfpv_v_{k}.so")
-        from __graft_entry__ import HIPCC_FLAGS
+        from __graft_entry__ import HIPCC_FLAGS, HIP_SRCS
         flags, extra = list(HIPCC_FLAGS), [f for f in VARIANTS[k] if not f.startswith("PRELOAD=")]
         for f in VARIANTS[k]:
             if f.startswith("PRELOAD="):
                 flags = [("-amdgpu-kernarg-preload-count=" + f.split("=")[1]) if x.startswith("-amdgpu-kernarg-preload-count=") else x for x in flags]
-        subprocess.run(["/opt/rocm/bin/hipcc", *flags, *extra, "-o", out, os.path.join(REPO, "fpyv_amd", "csrc", "fpv_hip.hip")], check=True)
+        subprocess.run(["/opt/rocm/bin/hipcc", *flags, *extra, "-o", out, *HIP_SRCS], check=True)
         print("built", out)
     sys.exit(0)
 import torch
@@ -57,6 +62,16 @@ for k in names:
     h = C.c_void_p(); rc = l.fpv_create(C.byref(cp), n, 0, C.byref(h)); assert rc == 0, l.fpv_last_error()
     L[k], H[k] = l, h
 ld = int(L[names[0]].fpv_recommended_ld(n))
+BYTES = 133
+if a.physics:
+    from fpyv_amd import physics
+    sets = physics.sample(cp, 5, 0, n, mass=(0.8, 1.2), thrust=(0.8, 1.2), drag=(0.8, 1.2), rates_lag=(0.8, 1.2), thrust_lag=(0.8, 1.2))
+    table = torch.zeros((_lib.FPV_PHYS_ROWS, ld), device=dev)
+    table[:, :n] = torch.from_numpy(physics.derive(cp, sets)).to(dev)
+    for k in names:
+        L[k].fpv_set_physics.argtypes = [C.c_void_p, C.c_void_p, C.c_int64]
+        rc = L[k].fpv_set_physics(H[k], table.data_ptr(), ld); assert rc == 0, L[k].fpv_last_error()
+    BYTES = 133 + 4 * (_lib.FPV_PHYS_ROWS - 2)
 rew = torch.zeros(n, device=dev); done = torch.zeros(n, dtype=torch.uint8, device=dev)
 if a.states > 1:
     # the same variants on several state matrices of this process, freed and allocated again in between: one line per matrix
@@ -106,4 +121,4 @@ for r in range(a.rounds):
 for k in names:
     for rot in a.rotations:
         med = statistics.median(res[(k, rot)])
-        print(f"n={n} {k:12s} rotation {rot:8d}: median {med:8.3f} us  min {min(res[(k, rot)]):8.3f} us   {133 * n / med / 1e3:8.1f} GB/s   bitwise==base {bool(torch.equal(fin[k][:, :n], fin[names[0]][:, :n]))}", flush=True)
+        print(f"n={n} {k:12s} rotation {rot:8d}: median {med:8.3f} us  min {min(res[(k, rot)]):8.3f} us   {BYTES * n / med / 1e3:8.1f} GB/s   bitwise==base {bool(torch.equal(fin[k][:, :n], fin[names[0]][:, :n]))}", flush=True)

@@ -6,6 +6,7 @@ the plain single-step kernel, the fp16-state single-step kernel and the plain k-
 
     python tools/hot_kernel_isa.py                     # prints the report
     python tools/hot_kernel_isa.py --write r05         # also writes profiles/r05_hot_kernel_isa.txt
+    python tools/hot_kernel_isa.py fpyv_amd/csrc/fpv_phys.hip      # another translation unit: every kernel of it
 
 tests/test_isa_claims.py runs the same functions and holds DESIGN.md to the numbers.
 """
@@ -25,11 +26,11 @@ HOT = collections.OrderedDict([
 ])
 
 
-def disassemble(path="/tmp/_fpv_claims.s"):
-    """(assembly text, remark text) of the whole library at the shipped flags."""
+def disassemble(path="/tmp/_fpv_claims.s", src=SRC):
+    """(assembly text, remark text) of one translation unit of the library (default: fpv_hip.hip) at the shipped flags."""
     from __graft_entry__ import HIPCC_FLAGS
     flags = [f for f in HIPCC_FLAGS if f not in ("-shared", "-fPIC")]
-    r = subprocess.run(["/opt/rocm/bin/hipcc"] + flags + ["-S", "--cuda-device-only", "-Rpass-analysis=kernel-resource-usage", "-o", path, SRC],
+    r = subprocess.run(["/opt/rocm/bin/hipcc"] + flags + ["-S", "--cuda-device-only", "-Rpass-analysis=kernel-resource-usage", "-o", path, src],
                        capture_output=True, text=True, check=True)
     return open(path).read(), r.stderr
 
@@ -107,9 +108,10 @@ def load_block(lines):
     return out
 
 
-def report():
-    asm, rem = disassemble()
+def report(src=SRC):
+    asm, rem = disassemble(src=src)
     bodies, res = kernel_bodies(asm), resources(rem)
+    hot = HOT if os.path.abspath(src) == SRC else collections.OrderedDict((n, n) for n in bodies)
     lines = ["# Hot-kernel ISA facts from a fresh disassembly (tools/hot_kernel_isa.py; hipcc flags of __graft_entry__.py)", ""]
     tot = collections.Counter()
     for b in bodies.values():
@@ -117,7 +119,7 @@ def report():
     lines.append(f"whole library, {len(bodies)} kernels: scratch/flat/buffer instructions {tot['scratch_flat_buffer']}, v_mfma {tot['mfma']}, "
                  f"SGPR-spill lane operations {tot['sgpr_spill_lane_ops']}, kernels with scratch > 0: {sum(1 for r in res.values() if r.get('scratch'))}, "
                  f"with spilled SGPRs: {sum(1 for r in res.values() if r.get('sspill'))}, with spilled VGPRs: {sum(1 for r in res.values() if r.get('vspill'))}")
-    for title, pat in HOT.items():
+    for title, pat in hot.items():
         name = next(n for n in bodies if pat in n)
         c, r = counts(bodies[name]), res.get(name, {})
         lines += ["", f"## {title}", f"static instruction counts (every path of the kernel, rare branches included): {dict(sorted(c.items()))}",
@@ -129,7 +131,7 @@ def report():
 
 
 if __name__ == "__main__":
-    text = report()
+    text = report(next((os.path.abspath(x) for x in sys.argv[1:] if x.endswith(".hip")), SRC))
     print(text)
     if "--write" in sys.argv:
         tag = sys.argv[sys.argv.index("--write") + 1]

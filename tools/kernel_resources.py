@@ -2,7 +2,8 @@
 """Print VGPR / SGPR / spills / occupancy / scratch of every gfx950 kernel in fpyv_amd/csrc/fpv_hip.hip
 (hipcc -Rpass-analysis=kernel-resource-usage; no GPU needed).
 
-    python tools/kernel_resources.py [name-filter] [-D...]      # extra -D flags go to hipcc
+    python tools/kernel_resources.py [name-filter] [-D...] [file.hip]     # extra -D flags go to hipcc; another translation
+                                                                          # unit (fpyv_amd/csrc/fpv_phys.hip) instead of fpv_hip.hip
 
 The compiler prints `TotalSGPRs:` (the round-2 version of this tool looked for ` SGPRs:`, matched only the
 `SGPRs Spill:` line by accident of ordering and showed -1 everywhere) and, separately, `SGPRs Spill:` /
@@ -20,10 +21,10 @@ KEYS = (("vgpr", r"remark:\s+VGPRs: (\d+)"), ("sgpr", r"remark:\s+TotalSGPRs: (\
         ("scratch", r"ScratchSize \[bytes/lane\]: (\d+)"), ("lds", r"LDS Size \[bytes/block\]: (\d+)"))
 
 
-def collect(extra_flags=()):
+def collect(extra_flags=(), src=SRC):
     sys.path.insert(0, REPO)
     from __graft_entry__ import HIPCC_FLAGS
-    cmd = ["/opt/rocm/bin/hipcc"] + HIPCC_FLAGS + list(extra_flags) + ["-Rpass-analysis=kernel-resource-usage", "-o", "/tmp/_fpv_res.so", SRC]
+    cmd = ["/opt/rocm/bin/hipcc"] + HIPCC_FLAGS + list(extra_flags) + ["-Rpass-analysis=kernel-resource-usage", "-o", "/tmp/_fpv_res.so", src]
     out = subprocess.run(cmd, capture_output=True, text=True).stderr
     rows = []
     for ln in out.splitlines():
@@ -43,8 +44,8 @@ def collect(extra_flags=()):
 
 
 def main():
-    flt = next((a for a in sys.argv[1:] if not a.startswith("-")), "")
-    rows = collect([a for a in sys.argv[1:] if a.startswith("-")])
+    flt = next((a for a in sys.argv[1:] if not a.startswith("-") and not a.endswith(".hip")), "")
+    rows = collect([a for a in sys.argv[1:] if a.startswith("-")], next((a for a in sys.argv[1:] if a.endswith(".hip")), SRC))
     print(f"{'kernel':86s} vgpr sgpr s-spill v-spill occ scratch lds")
     for r in rows:
         if flt in r["kernel"]:
