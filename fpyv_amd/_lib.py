@@ -26,6 +26,11 @@ RESET_POSE_ROWS = 10          # fpv_buffers_t.reset_pose: [10][ld] = p3 v3 q4 (w
 FPV_PHYS_ROWS = 13            # fpv_set_physics: [13][ld] derived constants per drone (fpv_abi.h FPV_PHYS_*)
 FPV_PHYS_INPUTS = 10          # a parameter set: mass, c3 c2 c1 c0, Cd x y z, rates_transition_rate, thrust_transition_rate
 PHYS_IN_MASS, PHYS_IN_C3, PHYS_IN_CD_X, PHYS_IN_RATES_LAG, PHYS_IN_THRUST_LAG = 0, 1, 5, 8, 9
+FPV_MAX_GATES = 64            # fpv_set_gates: a course has 1..64 gates
+FPV_GATE_FLOATS = 16          # a descriptor row: c3 n3 u3 w3 a hz zc r2 (fpv_abi.h "Gate courses")
+GATE_SHAPES = {"rectangle": 0, "circle": 1, "half_circle": 2}
+GATE_EVENT_NONE, GATE_EVENT_PASS, GATE_EVENT_MISS, GATE_EVENT_FINISH = 0, 1, 2, 3
+GATE_OBS_ROWS = 6
 FPV_HALF_PAIR_ROWS = 5
 FPV_HALF_HALVES = 11          # binary16 values per drone in state_h (5 pair rows + 1 half row)
 FPV_OBS_AOS_DIM = 16
@@ -41,7 +46,8 @@ EXPORTS = ("fpv_abi_version", "fpv_sizeof", "fpv_state_rows", "fpv_algorithmic_b
            "fpv_diag_stream_copy", "fpv_diag_stream_copy_wide", "fpv_diag_busy", "fpv_diag_xcd_map", "fpv_pid_reset", "fpv_pid_call", "fpv_comm_unique_id", "fpv_comm_create", "fpv_comm_destroy", "fpv_comm_info",
            "fpv_allgather_done", "fpv_allgather_f32", "fpv_last_error",
            "fpv_error_name", "fpv_encoding_id", "fpv_reset_pose_sample",
-           "fpv_physics_rows", "fpv_physics_derive", "fpv_physics_sample", "fpv_set_physics", "fpv_get_physics")
+           "fpv_physics_rows", "fpv_physics_derive", "fpv_physics_sample", "fpv_set_physics", "fpv_get_physics",
+           "fpv_gates_derive", "fpv_set_gates", "fpv_gate_eval")
 
 
 class FpvParams(C.Structure):
@@ -169,6 +175,38 @@ def pack_params(p, auto_reset: bool = False, fp16_state: bool = False, stick_noi
     return s
 
 
+class FpvGate(C.Structure):
+    """fpv_gate_t: what fpv_gates_derive reads (the reference's Gate(position, rotation_matrix, size, shape))."""
+    _fields_ = [("position", C.c_double * 3), ("rotation", C.c_double * 9), ("size", C.c_double), ("shape", C.c_int32),
+                ("_reserved", C.c_int32)]
+
+
+class FpvGateCourse(C.Structure):
+    """fpv_gate_course_t: a course as fpv_set_gates binds it (device pointers) or fpv_gate_eval reads it (host pointers)."""
+    _fields_ = [("struct_size", C.c_uint32), ("count", C.c_int32), ("descriptors", C.c_void_p), ("gate_word", C.c_void_p),
+                ("gate_obs", C.c_void_p), ("gate_obs_ld", C.c_int64), ("gate_start", C.c_void_p), ("laps", C.c_int32),
+                ("miss_is_done", C.c_int32), ("progress_gain", C.c_float), ("pass_bonus", C.c_float), ("finish_bonus", C.c_float),
+                ("miss_penalty", C.c_float), ("crash_penalty", C.c_float), ("_reserved", C.c_float)]
+
+
+GATE_REWARD_DEFAULTS = dict(progress=1.0, passed=10.0, finish=50.0, missed=5.0, crash=10.0)
+
+
+def pack_course(count: int, laps: int = 0, gate_rewards=None, miss_is_done: bool = False) -> FpvGateCourse:
+    """The constants of a course (the pointers are the caller's to fill): gate_rewards = dict(progress=, passed=, finish=,
+    missed=, crash=), each defaulting to GATE_REWARD_DEFAULTS."""
+    r = dict(GATE_REWARD_DEFAULTS)
+    unknown = set(gate_rewards or ()) - set(r)
+    if unknown:
+        raise ValueError(f"gate_rewards has no {sorted(unknown)}; its keys are {sorted(r)}")
+    r.update(gate_rewards or {})
+    c = FpvGateCourse()
+    c.struct_size, c.count, c.laps, c.miss_is_done = C.sizeof(FpvGateCourse), int(count), int(laps), int(bool(miss_is_done))
+    c.progress_gain, c.pass_bonus, c.finish_bonus = float(r["progress"]), float(r["passed"]), float(r["finish"])
+    c.miss_penalty, c.crash_penalty = float(r["missed"]), float(r["crash"])
+    return c
+
+
 class FpvCacheModel(C.Structure):
     """fpv_cache_model_t: what a device says about itself, held against the cache model of the rotation / row stride."""
     _fields_ = [("struct_size", C.c_uint32), ("matches", C.c_int32), ("compute_units", C.c_int32), ("xcds", C.c_int32),
@@ -253,10 +291,13 @@ def lib() -> C.CDLL:
     L.fpv_physics_sample.argtypes = [pp, C.c_uint64, C.c_uint64, i64, vp, vp]
     L.fpv_set_physics.argtypes = [vp, vp, i64]
     L.fpv_get_physics.argtypes = [vp, C.POINTER(vp), C.POINTER(i64)]
+    L.fpv_gates_derive.argtypes = [C.c_int, vp, vp]
+    L.fpv_set_gates.argtypes = [vp, C.POINTER(FpvGateCourse)]
+    L.fpv_gate_eval.argtypes = [C.POINTER(FpvGateCourse), i64, vp, vp, vp, vp, vp, C.c_int, vp, vp, vp, vp, vp, vp]
     if L.fpv_abi_version() != FPV_ABI_VERSION:
         raise ImportError(f"libfpv_hip.so ABI {L.fpv_abi_version()} != binding {FPV_ABI_VERSION} - rebuild the library "
                           "(`python -c 'import __graft_entry__ as g; g.build()'`)")
-    for which, struct in ((0, FpvParams), (1, FpvBuffers), (2, FpvObjects), (3, FpvPidParams), (4, FpvCacheModel)):
+    for which, struct in ((0, FpvParams), (1, FpvBuffers), (2, FpvObjects), (3, FpvPidParams), (4, FpvCacheModel), (5, FpvGateCourse)):
         if L.fpv_sizeof(which) != C.sizeof(struct):
             raise ImportError(f"{struct.__name__}: ctypes declares {C.sizeof(struct)} bytes, libfpv_hip.so has "
                               f"{L.fpv_sizeof(which)} - _lib.py and include/fpv_abi.h are out of step")

@@ -812,6 +812,9 @@ struct fpv_env {
     const float* phys = nullptr;
     int64_t phys_ld = 0;
     int phys_rows_last = 0;
+    // a gate course (fpv_set_gates): what the kernels of csrc/fpv_gate.hip read, copied from the caller's struct
+    bool gates = false;
+    FpvGateArgs ga = {};
 };
 
 // The kernels of csrc/fpv_phys.hip, by instantiation: weak, so that this file ALONE still links into a loadable library that
@@ -820,6 +823,12 @@ struct fpv_env {
 // "load the ground rows" bit in n_start (kPhysGroundBit); the k-step kernels take one FpvRollPhysArgs.
 extern "C" __attribute__((weak, visibility("hidden"))) void* fpv_phys_step_kernel(int noise, int obj);
 extern "C" __attribute__((weak, visibility("hidden"))) void* fpv_phys_roll_kernel(int noise, int obj);
+// The kernels of csrc/fpv_gate.hip, weak in the same way (fpv_set_gates says so when they are absent).  The single-step kernel
+// takes FPV_STEP_PARAMS with the word base in the state_h slot and one FpvGateArgs after them, the k-step kernels ([stick noise]
+// [object list]; the two together have none) one FpvRollGateArgs, the word reset (word, mask, start gates, count, n).
+extern "C" __attribute__((weak, visibility("hidden"))) void* fpv_gate_step_kernel(void);
+extern "C" __attribute__((weak, visibility("hidden"))) void* fpv_gate_roll_kernel(int noise, int obj);
+extern "C" __attribute__((weak, visibility("hidden"))) void* fpv_gate_reset_kernel_fn(void);
 
 namespace {
 
@@ -893,6 +902,13 @@ int check_buffers(const fpv_env* h, const fpv_buffers_t* b, bool need_action)  /
         if (b->obs_aos) return fail(FPV_EINVAL, "a physics table cannot be combined with the AoS head (obs_aos)");
         if (b->ld != h->phys_ld) return fail(FPV_EALIGN, "the physics table's row stride must be the state's (fpv_buffers_t.ld)");
     }
+    if (h->gates) {     // a gate course (fpv_abi.h): what the gate kernels do not carry is refused by name
+        if (b->pos_comp) return fail(FPV_EINVAL, "a gate course cannot be combined with Kahan rows (pos_comp)");
+        if (b->rotation_override) return fail(FPV_EINVAL, "a gate course cannot be combined with the guidance override (rotation_override)");
+        if (b->obs_aos) return fail(FPV_EINVAL, "a gate course cannot be combined with the AoS head (obs_aos)");
+        if (noise && b->objects && b->objects->count > 0)
+            return fail(FPV_EINVAL, "a gate course cannot be combined with stick noise AND an object list (either one alone is served)");
+    }
     if ((b->ep_return == nullptr) != (b->ep_length == nullptr))
         return fail(FPV_EINVAL, "ep_return and ep_length must be given together");
     if ((b->last_return || b->last_length) && !b->ep_return)
@@ -957,6 +973,9 @@ struct DeviceGuard {
 typedef void (*StepKernel)(float*, const int64_t, const float4*, const int64_t, uint16_t*, const int64_t, const FpvK, const FpvBufD);
 typedef void (*RollKernel)(const FpvRollArgs);
 typedef void (*PhysRollKernel)(const FpvRollPhysArgs);
+typedef void (*GateStepKernel)(float*, const int64_t, const float4*, const int64_t, uint32_t*, const int64_t, const FpvK, const FpvBufD, const FpvGateArgs);
+typedef void (*GateRollKernel)(const FpvRollGateArgs);
+typedef void (*GateResetKernel)(uint32_t*, const uint8_t*, const uint8_t*, const uint32_t, const int64_t);
 // blocks of one single-step launch: n's, in whole rounds of the eight XCDs - every single-step kernel (drone, fp16 state, AoS head,
 // Racer) reads n and the start block from one argument, and FPV_STEP_INDEX computes the same number from n
 inline int64_t step_grid(int64_t n) { return (n + 8 * kStepBlock - 1) / (8 * kStepBlock) * 8; }
@@ -1019,6 +1038,10 @@ RollKernel choose_rollout_kernel(const fpv_env* h, const FpvBufD& d)
 StepKernel choose_kernel(const fpv_env* h, const FpvBufD& d)
 {
     if (has_reset_source(h, d) && !d.obs_aos) return nullptr;      // routed around the pinned single-step kernels (see has_reset_source)
+    // a gate course: fpv_gate.hip's plain single-step kernel (launch_step / GraphNode pass it the ninth argument); with stick noise
+    // or an object list the k-step kernel with k = 1, like a reset source
+    if (h->gates)
+        return ((h->K.flags & FPV_FLAG_STICK_NOISE) || d.objs.count > 0) ? nullptr : reinterpret_cast<StepKernel>(fpv_gate_step_kernel());
     // a physics table: fpv_phys.hip's single-step kernel - the same argument layout, the table base in the state_h slot (step_slot5)
     if (h->phys) return reinterpret_cast<StepKernel>(fpv_phys_step_kernel((h->K.flags & FPV_FLAG_STICK_NOISE) != 0, d.objs.count > 0));
     if (h->mode != FPV_MODE_DRONE) return kRacerStep[h->K.r_wide != 0][h->K.r_pid_variant != 0];
@@ -1034,6 +1057,7 @@ StepKernel choose_kernel(const fpv_env* h, const FpvBufD& d)
 // and n | start block << 32, with kPhysGroundBit when a table launch loads the ground rows
 uint16_t* step_slot5(const fpv_env* h, const FpvBufD& d)
 {
+    if (h->gates) return reinterpret_cast<uint16_t*>(h->ga.word);
     return h->phys ? reinterpret_cast<uint16_t*>(const_cast<float*>(h->phys)) : d.state_h;
 }
 int64_t step_n_start(const fpv_env* h, const FpvBufD& d, int64_t start)
@@ -1048,7 +1072,13 @@ int launch_roll(fpv_env* h, const FpvBufD& d, const FpvRoll& R, hipStream_t s, c
     FpvRollArgs& args = pa.A;
     args.K = h->K; args.B = d; args.n = h->n; args.R = R;
     int rc;
-    if (h->phys) {
+    if (h->gates) {
+        FpvRollGateArgs ga;
+        memset(&ga, 0, sizeof(ga));
+        ga.A = args; ga.G = h->ga;
+        rc = launch(what, reinterpret_cast<GateRollKernel>(fpv_gate_roll_kernel((h->K.flags & FPV_FLAG_STICK_NOISE) != 0, d.objs.count > 0)),
+                    blocks_for(h->n, kStepBlock), dim3(kStepBlock), s, ga);
+    } else if (h->phys) {
         pa.phys = h->phys;
         pa.ground = phys_ground(h, d) ? 1 : 0;
         h->phys_rows_last = phys_rows(h, d);
@@ -1074,8 +1104,10 @@ int launch_step(fpv_env* h, const FpvBufD& d_in, hipStream_t s)
     h->rot_blocks = rotation_blocks(h, &d);
     const int64_t start = h->rot_blocks > 0 ? h->start_block % nblk : 0;
     if (h->phys) h->phys_rows_last = phys_rows(h, d);
-    const int rc = launch("step kernel launch", f, dim3((unsigned)nblk), dim3(kStepBlock), s, d.state, d.ld, d.action, d.action_ld, step_slot5(h, d),
-                          step_n_start(h, d, start), h->K, d);
+    const int rc = h->gates ? launch("step kernel launch", reinterpret_cast<GateStepKernel>(fpv_gate_step_kernel()), dim3((unsigned)nblk), dim3(kStepBlock), s, d.state, d.ld,
+                                     d.action, d.action_ld, h->ga.word, step_n_start(h, d, start), h->K, d, h->ga)
+                            : launch("step kernel launch", f, dim3((unsigned)nblk), dim3(kStepBlock), s, d.state, d.ld, d.action, d.action_ld,
+                                     step_slot5(h, d), step_n_start(h, d, start), h->K, d);
     if (rc != FPV_OK) return rc;
     ++h->launches;                     // a refused launch leaves the step index where it was
     if (h->rot_blocks > 0) h->start_block = (start + nblk - h->rot_blocks % nblk) % nblk;
@@ -1171,6 +1203,7 @@ int64_t written_bytes_per_drone(const fpv_env* h, const FpvBufD* d)
 {
     int64_t b = state_bytes(h->mode, &h->K);
     if (h->K.flags & FPV_FLAG_STICK_NOISE) b += 16;            // the four EMA rows
+    if (h->gates) b += 4;                                       // the gate word (the obs rows are streaming stores, like accel)
     if (!d) return b + 5;
     if (d->reward) b += 4;
     if (d->done) b += 1;
@@ -1242,10 +1275,11 @@ struct GraphNode {
     FpvK K;
     int64_t n_start;
     uint16_t* slot5;
-    void* args[8];
+    FpvGateArgs ga;         // the ninth parameter of the gate kernel (the others have eight and do not read it)
+    void* args[9];
     hipKernelNodeParams np;
     GraphNode(const fpv_env* h, const FpvBufD& dt, int t)
-        : d(dt), K(h->K), slot5(step_slot5(h, dt)), args{&d.state, &d.ld, &d.action, &d.action_ld, &slot5, &n_start, &K, &d}
+        : d(dt), K(h->K), slot5(step_slot5(h, dt)), ga(h->ga), args{&d.state, &d.ld, &d.action, &d.action_ld, &slot5, &n_start, &K, &d, &ga}
     {
         const int64_t nblk = step_grid(h->n), rot = rotation_blocks(h, &d);
         const int64_t start = rot > 0 ? (int64_t)(((uint64_t)t * (uint64_t)(nblk - rot % nblk)) % (uint64_t)nblk) : 0;
@@ -1301,7 +1335,8 @@ int fpv_sizeof(int which)
         case 2: return (int)sizeof(fpv_objects_t);
         case 3: return (int)sizeof(fpv_pid_params_t);
         case 4: return (int)sizeof(fpv_cache_model_t);
-        default: return fail(FPV_EINVAL, "fpv_sizeof: 0 = fpv_params_t, 1 = fpv_buffers_t, 2 = fpv_objects_t, 3 = fpv_pid_params_t, 4 = fpv_cache_model_t");
+        case 5: return (int)sizeof(fpv_gate_course_t);
+        default: return fail(FPV_EINVAL, "fpv_sizeof: 0 = fpv_params_t, 1 = fpv_buffers_t, 2 = fpv_objects_t, 3 = fpv_pid_params_t, 4 = fpv_cache_model_t, 5 = fpv_gate_course_t");
     }
 }
 
@@ -1324,7 +1359,9 @@ int fpv_handle_algorithmic_bytes(fpv_handle_t h)
     // the rows the selected kernel actually moves (fp16 state: 89); a physics table: + the rows the last launch loaded (before
     // the first launch: what the handle's flags alone ask for)
     const int rows = !h->phys ? 0 : h->phys_rows_last ? h->phys_rows_last : (h->K.flags & FPV_FLAG_GROUND) ? FPV_PHYS_ROWS : FPV_PHYS_ROWS - 2;
-    return algorithmic_bytes(h->mode, &h->K) + 4 * rows;
+    // a gate course: the word read and written, and the six observation rows when they are bound
+    const int gate = !h->gates ? 0 : 8 + (h->ga.obs ? 24 : 0);
+    return algorithmic_bytes(h->mode, &h->K) + 4 * rows + gate;
 }
 
 int fpv_physics_rows(void) { return FPV_PHYS_ROWS; }
@@ -1364,6 +1401,7 @@ int fpv_set_physics(fpv_handle_t h, const float* table, int64_t ld)
         return fail(FPV_EINVAL, "per-drone physics is not in this build (the library was linked without csrc/fpv_phys.hip)");
     if (!h) return fail(FPV_EINVAL, "null handle");
     if (table) {
+        if (h->gates) return fail(FPV_EINVAL, "a physics table cannot be combined with a gate course (fpv_set_gates)");
         if (h->mode != FPV_MODE_DRONE) return fail(FPV_EINVAL, "a physics table cannot be combined with Racer mode");
         if (h->K.flags & FPV_FLAG_FP16_STATE) return fail(FPV_EINVAL, "a physics table cannot be combined with fp16 state (FPV_FLAG_FP16_STATE)");
         if ((uintptr_t)table & 15) return fail(FPV_EALIGN, "the physics table must be 16-byte aligned");
@@ -1381,6 +1419,106 @@ int fpv_get_physics(fpv_handle_t h, const float** table, int64_t* ld)
 {
     if (!h || !table || !ld) return fail(FPV_EINVAL, "null argument");
     *table = h->phys; *ld = h->phys_ld;
+    return FPV_OK;
+}
+
+int fpv_gates_derive(int count, const fpv_gate_t* gates, float* out_rows)
+{
+    if (!gates || !out_rows) return fail(FPV_EINVAL, "null argument");
+    if (count < 1 || count > FPV_MAX_GATES) return fail(FPV_EPARAM, "a course has 1.." + std::to_string(FPV_MAX_GATES) + " gates, not " + std::to_string(count));
+    for (int k = 0; k < count; ++k) {
+        const char* why = "";
+        const int rc = fpv_derive_gate_row(gates[k], out_rows + (int64_t)k * FPV_GATE_FLOATS, &why);
+        if (rc != FPV_OK) return fail(rc, "gate " + std::to_string(k) + ": " + why);
+    }
+    return FPV_OK;
+}
+
+namespace {
+
+// the uniform constants of a course, checked: FPV_OK or the error
+int gate_constants(const fpv_gate_course_t* c, FpvGateK* G)
+{
+    if (c->struct_size != sizeof(fpv_gate_course_t)) return fail(FPV_EINVAL, "fpv_gate_course_t.struct_size does not match this library");
+    if (c->count < 1 || c->count > FPV_MAX_GATES) return fail(FPV_EPARAM, "a course has 1.." + std::to_string(FPV_MAX_GATES) + " gates, not " + std::to_string(c->count));
+    if (c->laps < 0 || (int64_t)c->laps * c->count > (int64_t)FPV_GATE_MAX_PASSED)
+        return fail(FPV_EPARAM, "laps must be >= 0 and laps * count at most 2^22 - 1 (the word counts the gates passed in 22 bits)");
+    const float r[5] = {c->progress_gain, c->pass_bonus, c->finish_bonus, c->miss_penalty, c->crash_penalty};
+    for (const float x : r)
+        if (!isfinite(x)) return fail(FPV_EPARAM, "a reward constant of the course is not finite");
+    memset(G, 0, sizeof(*G));
+    G->progress_gain = c->progress_gain; G->pass_bonus = c->pass_bonus; G->finish_bonus = c->finish_bonus;
+    G->miss_penalty = c->miss_penalty; G->crash_penalty = c->crash_penalty;
+    G->count = (uint32_t)c->count; G->finish_at = (uint32_t)(c->laps * c->count); G->miss_done = c->miss_is_done ? 1u : 0u;
+    return FPV_OK;
+}
+
+}  // namespace
+
+int fpv_set_gates(fpv_handle_t h, const fpv_gate_course_t* c)
+{
+    if (c && (!fpv_gate_step_kernel || !fpv_gate_roll_kernel || !fpv_gate_reset_kernel_fn))      // (asked first: what a build without the kernels answers to any bind)
+        return fail(FPV_EINVAL, "gate courses are not in this build (the library was linked without csrc/fpv_gate.hip)");
+    if (!h) return fail(FPV_EINVAL, "null handle");
+    if (!c) {
+        h->gates = false;
+        memset(&h->ga, 0, sizeof(h->ga));
+        update_rotation(h);
+        h->graph_shape_key.clear();
+        return FPV_OK;
+    }
+    FpvGateArgs a;
+    memset(&a, 0, sizeof(a));          // padding bytes are part of the graph-cache key
+    const int rc = gate_constants(c, &a.K);
+    if (rc != FPV_OK) return rc;
+    if (h->mode != FPV_MODE_DRONE) return fail(FPV_EINVAL, "a gate course cannot be combined with Racer mode");
+    if (h->K.flags & FPV_FLAG_FP16_STATE) return fail(FPV_EINVAL, "a gate course cannot be combined with fp16 state (FPV_FLAG_FP16_STATE)");
+    if (h->phys) return fail(FPV_EINVAL, "a gate course cannot be combined with a physics table (fpv_set_physics)");
+    if (!c->descriptors || !c->gate_word) return fail(FPV_EINVAL, "fpv_gate_course_t.descriptors and gate_word must be given");
+    if ((uintptr_t)c->descriptors & 15) return fail(FPV_EALIGN, "the gate descriptors must be 16-byte aligned");
+    if (((uintptr_t)c->gate_word & 3) || ((uintptr_t)c->gate_obs & 3)) return fail(FPV_EALIGN, "gate_word and gate_obs must be 4-byte aligned");
+    if (c->gate_obs && c->gate_obs_ld < h->n) return fail(FPV_EALIGN, "gate_obs_ld is smaller than the number of drones");
+    a.tab = reinterpret_cast<const fpv_gate_v4*>(c->descriptors);
+    a.word = c->gate_word; a.obs = c->gate_obs; a.obs_ld = c->gate_obs ? c->gate_obs_ld : 0; a.start = c->gate_start;
+    h->ga = a;
+    h->gates = true;
+    update_rotation(h);
+    h->graph_shape_key.clear();         // a cached graph carries the kernels and the course of the old binding
+    return FPV_OK;
+}
+
+int fpv_gate_eval(const fpv_gate_course_t* c, int64_t n, const float* p_old, const float* p_new, const float* q_new,
+                  const uint8_t* physics_done, const uint32_t* word_in, int auto_reset, const float* p_after, const float* q_after,
+                  uint32_t* word_out, float* reward, uint8_t* done, float* obs)
+{
+    if (!c || !p_old || !p_new || !q_new || !word_in || !word_out || !reward || !done) return fail(FPV_EINVAL, "null argument");
+    if (n <= 0) return fail(FPV_EINVAL, "n must be positive");
+    FpvGateK G;
+    const int rc = gate_constants(c, &G);
+    if (rc != FPV_OK) return rc;
+    if (!c->descriptors) return fail(FPV_EINVAL, "fpv_gate_course_t.descriptors must be given (host memory)");
+    alignas(16) float rows[FPV_MAX_GATES * FPV_GATE_FLOATS];
+    memcpy(rows, c->descriptors, sizeof(float) * FPV_GATE_FLOATS * (size_t)c->count);
+    const fpv_gate_v4* tab = reinterpret_cast<const fpv_gate_v4*>(rows);
+    for (int64_t i = 0; i < n; ++i) {
+        const float* po = p_old + 3 * i; const float* pn = p_new + 3 * i;
+        const uint32_t g = fpv_gate_index(word_in[i], G.count);
+        const fpv_gate_v4* d = tab + g * FPV_GATE_GROUPS;
+        const FpvGateOut o = fpv_gate_step<true>(G, fpv_gate_cn(d), d, word_in[i], po[0], po[1], po[2], pn[0], pn[1], pn[2],
+                                                 physics_done && physics_done[i]);
+        uint32_t w = o.word;
+        const float* pa = pn; const float* qa = q_new + 4 * i;
+        if (auto_reset && o.done) {
+            w = fpv_gate_word_reset(w, c->gate_start ? (uint32_t)c->gate_start[i] : 0u, G.count);
+            if (p_after) pa = p_after + 3 * i;
+            if (q_after) qa = q_after + 4 * i;
+        }
+        word_out[i] = w; reward[i] = o.reward; done[i] = o.done ? 1 : 0;
+        if (obs) {
+            FpvQuat q; q.w = qa[0]; q.x = qa[1]; q.y = qa[2]; q.z = qa[3];
+            fpv_gate_obs(fpv_gate_cn(tab + fpv_gate_index(w, G.count) * FPV_GATE_GROUPS), q, pa[0], pa[1], pa[2], obs + 6 * i);
+        }
+    }
     return FPV_OK;
 }
 
@@ -1546,8 +1684,12 @@ int fpv_reset(fpv_handle_t h, const fpv_buffers_t* b, const uint8_t* mask, const
     if (dev.rc != FPV_OK) return dev.rc;
     FpvBufD d = to_device_view(h, b);
     d.step = h->launches;                // the jitter of an explicit reset is keyed by the handle's step counter
-    return launch("reset kernel launch", fpv_reset_kernel, blocks_for(h->n, kBlock), dim3(kBlock), (hipStream_t)stream, h->K, d,
-                  h->mode, mask, position, velocity, ypr_deg, h->n);
+    rc = launch("reset kernel launch", fpv_reset_kernel, blocks_for(h->n, kBlock), dim3(kBlock), (hipStream_t)stream, h->K, d,
+                h->mode, mask, position, velocity, ypr_deg, h->n);
+    if (rc != FPV_OK || !h->gates) return rc;
+    // a gate course: the words of the same lanes, after the state on the same stream
+    return launch("gate word reset launch", reinterpret_cast<GateResetKernel>(fpv_gate_reset_kernel_fn()), blocks_for(h->n, kBlock), dim3(kBlock),
+                  (hipStream_t)stream, h->ga.word, mask, h->ga.start, h->ga.K.count, h->n);
 }
 
 int fpv_step(fpv_handle_t h, const fpv_buffers_t* b, void* stream)
@@ -1666,6 +1808,8 @@ int fpv_rollout_graph(fpv_handle_t h, const fpv_buffers_t* b, int k, int64_t act
     // the issued launches when the AoS head is written (fpv_step_n writes none)
     if (b->reset_pose || (h->K.flags & FPV_FLAG_RESET_JITTER))
         return b->obs_aos ? fpv_rollout(h, b, k, action_stride, out_stride, stream) : fpv_step_n(h, b, k, action_stride, out_stride, stream);
+    // and for a gate course with an object list, whose single steps are the k-step kernel's
+    if (h->gates && b->objects && b->objects->count > 0) return fpv_step_n(h, b, k, action_stride, out_stride, stream);
     const DeviceGuard dev(h->device);
     if (dev.rc != FPV_OK) return dev.rc;
     const FpvBufD d0 = to_device_view(h, b);
@@ -1680,6 +1824,7 @@ int fpv_rollout_graph(fpv_handle_t h, const fpv_buffers_t* b, int k, int64_t act
     shape.append(reinterpret_cast<const char*>(wind), sizeof(wind));
     const int64_t table[2] = {(int64_t)(uintptr_t)h->phys, h->phys_ld};              // a bound physics table (fpv_set_physics)
     shape.append(reinterpret_cast<const char*>(table), sizeof(table));
+    if (h->gates) shape.append(reinterpret_cast<const char*>(&h->ga), sizeof(h->ga));           // a bound course (fpv_set_gates; zero-padded there)
     // everything else in the view is a buffer address
     const std::string ptrs(reinterpret_cast<const char*>(&d0), sizeof(d0));
     if (!h->graph_exec || shape != h->graph_shape_key) {

@@ -14,6 +14,7 @@
 #include "fpv_addr.h"
 #include "fpv_exp.h"
 #include "fpv_math.h"
+#include "fpv_gate.h"
 
 namespace {
 
@@ -375,5 +376,13 @@ struct FpvRollPhysArgs { FpvRollArgs A; const float* phys; int32_t ground; int32
 // single-step kernels: n <= 2^28, so bit 31 of n_start's low word is free - "this launch loads the two ground rows", decided on
 // the host and read from a preloaded SGPR: no scalar load stands between the wave's start and its table loads
 constexpr int64_t kPhysGroundBit = (int64_t)1 << 31;
+
+// ---- gate courses (csrc/fpv_gate.hip; launched from fpv_hip.hip) ----
+// what fpv_set_gates binds, as the kernels read it: the descriptor table, the word row, the optional observation rows and start
+// gates, the course's uniform constants.  The single-step kernel takes FPV_STEP_PARAMS with the word base in the state_h slot - a
+// gate handle has no fp16 state - and this struct as a ninth parameter; the k-step kernels take one FpvRollGateArgs, the
+// arguments of fpv_drone_rollout_kernel first (the views above read them at the same offsets).
+struct FpvGateArgs { const fpv_gate_v4* tab; uint32_t* word; float* obs; int64_t obs_ld; const uint8_t* start; FpvGateK K; };
+struct FpvRollGateArgs { FpvRollArgs A; FpvGateArgs G; };
 
 }  // namespace

@@ -215,7 +215,8 @@ class _Batch(_Handle):
                  fp16_state: bool = False, rounding_seed: int = 0, with_obs_aos: bool = False,
                  stick_noise: bool = False, noise_seed: int = 0, drone_id_offset: int = 0,
                  with_action_out: bool = False, kahan_position: bool = False, per_drone_reset_pose: bool = False,
-                 per_drone_physics: bool = False):
+                 per_drone_physics: bool = False, gates: Any = None, laps: int = 0, gate_rewards: Optional[Dict[str, float]] = None,
+                 miss_is_done: bool = False, gate_obs: bool = True, gate_start: Any = None):
         if num_envs <= 0:
             raise ValueError("num_envs must be positive")
         device = torch.device(device)
@@ -287,6 +288,22 @@ class _Batch(_Handle):
         self._override_keep = None
         self._done_bits_keep = None
         self._fill_buffers()
+        # a gate course (fpv_set_gates): the race state is one word per drone, `gate_word`; `gate_desc` holds the descriptor rows
+        # of up to 64 gates, `gate_obs_rows` [6, ld] the optional observation rows, `gate_start` [n] the optional start gates
+        self.gate_word = self.gate_desc = self.gate_obs_rows = self.gate_start = None
+        self._course = self._course_kw = None
+        if gates is not None:
+            i32 = dict(dtype=torch.int32, device=self.device)
+            self.gate_desc = torch.zeros((_lib.FPV_MAX_GATES, _lib.FPV_GATE_FLOATS), **f32)
+            self.gate_obs_rows = torch.zeros((_lib.GATE_OBS_ROWS, self.ld), **f32) if gate_obs else None
+            if gate_start is not None:
+                st = torch.as_tensor(np.asarray(gate_start) if not torch.is_tensor(gate_start) else gate_start, device=self.device)
+                self.gate_start = st.to(torch.uint8).expand(self.n).contiguous()
+                self.gate_word = self.gate_start.to(torch.int32)
+            else:
+                self.gate_word = torch.zeros(self.n, **i32)
+            self._course_kw = dict(laps=int(laps), gate_rewards=dict(gate_rewards or {}), miss_is_done=bool(miss_is_done))
+            self.set_gates(gates)
 
     # -- plumbing ---------------------------------------------------------------------------------
     def _fill_buffers(self) -> None:
@@ -368,7 +385,7 @@ class _Batch(_Handle):
 
     # -- checkpoint / resume (the reference has none; state is just tensors here) ------------------
     _CKPT_TENSORS = ("state", "state_h", "reward", "done", "ep_return", "ep_length", "last_return",
-                     "last_length", "noise_state", "pos_comp", "reset_pose", "physics")
+                     "last_length", "noise_state", "pos_comp", "reset_pose", "physics", "gate_word", "gate_start", "gate_desc")
     _CKPT_ROW_TENSORS = ("state", "noise_state", "pos_comp", "reset_pose", "physics")        # [rows, ld]: stored as their logical columns [rows, num_envs]
 
     def _state_h_views(self, t: Optional[torch.Tensor] = None, ld: Optional[int] = None):
@@ -395,6 +412,8 @@ class _Batch(_Handle):
                 d[k] = self._storage_words(self.n)
             else:
                 d[k] = t.clone()
+        if self._course is not None:                                     # the course's constants (its rows are `gate_desc`)
+            d["gate_course"] = dict(self._course_kw, count=int(self._course.count))
         d["step_counter"] = int(self._steps_launched)
         d["num_envs"], d["mode"] = self.n, self.mode
         d["layout"], d["ld"] = CHECKPOINT_LAYOUT, self.ld                # ld: for the record only - load does not need it
@@ -458,7 +477,63 @@ class _Batch(_Handle):
                     thrust[:self.n].copy_(ot[:self.n])
             else:
                 mine.copy_(src)
+        if "gate_course" in d:
+            if self.gate_word is None:
+                raise ValueError("checkpoint has a gate course but this batch was built without gates=")
+            kw = dict(d["gate_course"])
+            count = int(kw.pop("count"))
+            if self._course is None or kw != self._course_kw or count != int(self._course.count):
+                self._course_kw = kw
+                self._bind_course(count)
         self.set_step_counter(d["step_counter"])
+
+    # -- gate courses ------------------------------------------------------------------------------
+    def _bind_course(self, count: int) -> None:
+        c = _lib.pack_course(count, **self._course_kw)
+        c.descriptors, c.gate_word = self.gate_desc.data_ptr(), self.gate_word.data_ptr()
+        if self.gate_obs_rows is not None:
+            c.gate_obs, c.gate_obs_ld = self.gate_obs_rows.data_ptr(), self.ld
+        if self.gate_start is not None:
+            c.gate_start = self.gate_start.data_ptr()
+        _lib.check(self._L.fpv_set_gates(self._handle, C.byref(c)))
+        self._course = c
+
+    def set_gates(self, gates) -> None:
+        """The course of the steps enqueued from now on: a list of 1..64 `objects.Gate`s, or None to fly without a course again
+        (the handle then runs exactly the kernels it ran before; `gate_word` keeps its last values).  The descriptor rows are
+        re-derived (fpyv_amd.gates.derive) and uploaded on torch's current stream - gates that move are re-set between steps, like
+        a moving Target is re-bound.  Needs a batch built with gates=."""
+        if self.gate_word is None:
+            raise ValueError("this batch was built without gates=")
+        if gates is None:
+            _lib.check(self._L.fpv_set_gates(self._handle, None))
+            self._course = None
+            return
+        from . import gates as _gates
+        rows = _gates.derive(gates)
+        self.gate_desc[:rows.shape[0]].copy_(torch.from_numpy(rows))
+        if self._course is None or int(self._course.count) != rows.shape[0]:
+            self._bind_course(rows.shape[0])
+
+    @property
+    def gate_index(self) -> Optional[torch.Tensor]:
+        """[num_envs] the gate every drone has to pass next"""
+        return None if self.gate_word is None else self.gate_word & 0xFF
+
+    @property
+    def gate_event(self) -> Optional[torch.Tensor]:
+        """[num_envs] what the last step was for the race: 0 nothing, 1 PASS, 2 MISS, 3 FINISH (_lib.GATE_EVENT_*)"""
+        return None if self.gate_word is None else (self.gate_word >> 8) & 3
+
+    @property
+    def gates_passed(self) -> Optional[torch.Tensor]:
+        """[num_envs] gates passed in the running episode"""
+        return None if self.gate_word is None else (self.gate_word >> 10) & 0x3FFFFF
+
+    @property
+    def gate_obs(self) -> Optional[torch.Tensor]:
+        """[num_envs, 6] view: the next gate in the drone's body frame, R^T (c - p) and R^T n (None without gate_obs=True)"""
+        return None if self.gate_obs_rows is None else self.gate_obs_rows[:, :self.n].t()
 
     # -- raw stepping -----------------------------------------------------------------------------
     def _reset_raw(self, mask=None, position=None, velocity=None, ypr=None) -> None:
@@ -701,6 +776,17 @@ class _Partition(_Handle):
         b.done_bits_stride = 0
         if self.parent.physics is not None:            # this partition's column range of the one table
             _lib.check(self._L.fpv_set_physics(self._handle, self.parent.physics.data_ptr() + 4 * lo, pb.ld))
+        pc = getattr(self.parent, "_course", None)     # the parent's course on this partition's columns of the word and obs rows
+        if pc is not None:
+            c = _lib.FpvGateCourse.from_buffer_copy(pc)
+            c.gate_word = pc.gate_word + 4 * lo
+            c.gate_obs = off(pc.gate_obs, 4)
+            c.gate_start = off(pc.gate_start, 1)
+            _lib.check(self._L.fpv_set_gates(self._handle, C.byref(c)))
+            self._course = c
+        elif getattr(self, "_course", None) is not None:
+            _lib.check(self._L.fpv_set_gates(self._handle, None))
+            self._course = None
 
 
 def partition_bounds(n: int, parts: int) -> Sequence[Tuple[int, int]]:
@@ -1063,6 +1149,17 @@ class FpvVecEnv:
         """DroneBatch.randomize_physics for the whole population, ordered after steps in flight like reset."""
         self._whole_population(self.batch.randomize_physics, seed, **kw)
 
+    def set_gates(self, gates) -> None:
+        """DroneBatch.set_gates for the whole population (built with gates=), ordered after steps in flight like reset."""
+        self._whole_population(self.batch.set_gates, gates)
+        for P in self._parts:
+            P.rebind()
+
+    @property
+    def gate_obs(self) -> Optional[torch.Tensor]:
+        """[num_envs, 6] view of the gate observation rows (DroneBatch.gate_obs)"""
+        return self.batch.gate_obs
+
     def _whole_population(self, fn, *a, **kw) -> None:
         if not self._parts:
             fn(*a, **kw)
@@ -1101,6 +1198,9 @@ class FpvVecEnv:
             whole = lo == 0 and hi == batch.n
             info["episode_return"] = batch.last_return if whole else batch.last_return[lo:hi]
             info["episode_length"] = batch.last_length if whole else batch.last_length[lo:hi]
+        if getattr(batch, "gate_word", None) is not None:              # a gate course: the race state after this step
+            w = batch.gate_word[lo:hi]
+            info["gates_passed"], info["gate_event"] = (w >> 10) & 0x3FFFFF, (w >> 8) & 3
         return info
 
     # -- split phase ------------------------------------------------------------------------------

@@ -13,8 +13,9 @@ Analytic counterparts of the reference's world classes, keeping only what `handl
 The rendering arguments (sizes of point clouds, icosphere subdivision, resolutions) are accepted so the
 reference's own call sites (src/core/simulator.py:53-58, src/utils/generators.py) construct these classes
 unchanged, and are ignored: point clouds, rendering and bounding boxes are out of scope.  Gates and the
-Trail never collide in the reference (components.py:202); they exist here only so that an `object_list`
-built by the reference's code can be passed as is - `to_rows` skips them.
+Trail never collide in the reference (components.py:202): `to_rows` skips them, so an `object_list` built by the
+reference's code can be passed as is.  A Gate keeps the reference's plane geometry (normal, calculate_distance) and
+describes itself to the gate-course kernels (`as_gate_row`, fpyv_amd.gates).
 """
 from __future__ import annotations
 
@@ -78,11 +79,41 @@ class Target:
 
 
 class Gate:
-    """Never collides (components.py:202): carried through an object_list and skipped."""
+    """The reference's Gate (components.py:784-830) without its rendering: centre `position`, `rotation_matrix` (body -> world;
+    the gate's normal is its first column, the aperture lies in the plane of the other two), `size`, `shape` ("rectangle",
+    "circle", "half_circle").  It never collides (components.py:202): carried through an object_list and skipped.  A list of
+    gates is a COURSE for `DroneBatch(gates=...)` (fpyv_amd.gates)."""
     collides = False
 
     def __init__(self, position, rotation_matrix, size, shape: str = "rectangle", resolution: int = 17):
         self.position, self.rotation_matrix, self.size, self.shape = position, rotation_matrix, size, shape
+
+    @property
+    def normal(self) -> np.ndarray:
+        return np.asarray(self.rotation_matrix, dtype=np.float64)[:, 0]                      # components.py:812-813
+
+    def calculate_plane_equation(self) -> np.ndarray:
+        n = self.normal
+        return np.append(n, -np.dot(n, np.asarray(self.position, dtype=np.float64)))       # components.py:815-817
+
+    def calculate_distance(self, point) -> Any:
+        """signed distance of `point` ([3] or [..., 3]) to the gate's plane, positive on the side the normal points to"""
+        n = self.normal
+        return np.dot(np.asarray(point, dtype=np.float64), n) - np.dot(n, np.asarray(self.position, dtype=np.float64))   # :819-822
+
+    def shape_code(self) -> int:
+        """FPV_GATE_RECTANGLE / _CIRCLE / _HALF_CIRCLE, read like the reference reads the string (components.py:790-802)"""
+        if self.shape == "rectangle":
+            return _lib.GATE_SHAPES["rectangle"]
+        if "circle" in self.shape:
+            return _lib.GATE_SHAPES["half_circle" if "half" in self.shape else "circle"]
+        raise NotImplementedError(f"gate shape {self.shape!r}")
+
+    def as_gate_row(self) -> Tuple[Tuple[float, ...], Tuple[float, ...], float, int]:
+        """(position[3], rotation_matrix row-major [9], size, shape code): what fpv_gates_derive reads (fpv_gate_t)"""
+        R = np.asarray(self.rotation_matrix, dtype=np.float64).reshape(3, 3)
+        return (tuple(float(x) for x in np.asarray(self.position, dtype=np.float64).reshape(3)), tuple(float(x) for x in R.reshape(9)),
+                float(self.size), self.shape_code())
 
 
 class Trail:

@@ -314,7 +314,7 @@ typedef struct fpv_env* fpv_handle_t;
 
 int fpv_abi_version(void);
 /* sizeof of the ABI structs as this library was compiled (0 fpv_params_t, 1 fpv_buffers_t, 2 fpv_objects_t,
- * 3 fpv_pid_params_t):
+ * 3 fpv_pid_params_t, 4 fpv_cache_model_t, 5 fpv_gate_course_t):
  * lets a foreign-language binding verify its struct declarations at load time */
 int fpv_sizeof(int which);
 /* rows of the state matrix for a mode (FPV_DRONE_ROWS / FPV_RACER_ROWS), or FPV_EINVAL */
@@ -454,6 +454,88 @@ int fpv_set_params(fpv_handle_t h, const fpv_params_t* params);
  * binding back (NULL / 0 = none). */
 int fpv_set_physics(fpv_handle_t h, const float* table, int64_t ld);
 int fpv_get_physics(fpv_handle_t h, const float** table, int64_t* ld);
+
+/* ---- Gate courses (drone mode, fp32 state; functions only - FPV_ABI_VERSION, fpv_params_t and fpv_buffers_t are those of ABI 9)
+ * A handle may be given a COURSE: an ordered list of 1..FPV_MAX_GATES gates that every drone flies through in order.  The race
+ * costs one 32-bit word per drone (gate_word[n]) that the step kernels read and write with the state; the crossing test runs in
+ * the step kernel on the position before and after the update (csrc/fpv_gate.h fpv_gate_step: ONE function, the kernels' and
+ * fpv_gate_eval's).  The semantics are this build's (the reference has gates but no race); the geometry is the reference's Gate
+ * (components.py:784-830): centre c = position, normal n = rotation_matrix[:,0], in-plane axes u, w = columns 1 and 2.
+ *
+ * Descriptor row of a gate, FPV_GATE_FLOATS fp32 = four 16-byte groups (fpv_gates_derive writes it):
+ *     [0..2] c   [3..5] n   [6..8] u   [9..11] w   [12] a   [13] hz   [14] zc   [15] r2
+ * aperture (y = u.x, z = w.x of the crossing point x relative to c):  |y| <= a  and  |z| <= hz  and  y^2 + (z - zc)^2 <= r2
+ *     rectangle    a = hz = size/2            zc = 0         r2 = +inf                 (components.py:791)
+ *     circle       a = hz = size/2            zc = 0         r2 = (size/2)^2           (:793-798)
+ *     half_circle  a = size, hz = size/2      zc = -size/2   r2 = size^2               (:793-800)
+ *
+ * gate_word:  bits 0..7 the NEXT gate index, bits 8..9 the EVENT of the step just executed, bits 10..31 gates passed this episode.
+ * A step, with g = next gate before the step, p_old the position rows as loaded, p_new the position after the update and before
+ * any reset:  s0 = n.(p_old - c), s1 = n.(p_new - c); a FORWARD crossing is s0 < 0 && s1 >= 0 (a backward one is ignored); then
+ * t = s0 / (s0 - s1), x = (p_old - c) + t (p_new - p_old), and the event is PASS when (u.x, w.x) is in the aperture, else MISS.
+ * Only gate g is tested: at most one event per step.  PASS: passed += 1 (saturating at 2^22 - 1), next = (g + 1) mod count, and
+ * FINISH instead of PASS when laps > 0 and passed == laps * count.
+ *   reward = progress_gain (|p_old - c_g| - |p_new - c_g|) + pass_bonus [PASS or FINISH] + finish_bonus [FINISH]
+ *            - miss_penalty [MISS] - crash_penalty [physics done]                       (replaces -|p - goal| on a gate handle)
+ *   done   = physics done  or  FINISH  or  (MISS and miss_is_done); every done auto-resets like today's.
+ * Any reset of a lane (in-kernel, or fpv_reset for its masked lanes) sets passed = 0 and next = gate_start[i] (when bound and
+ * < count, else 0); the event bits still describe the step that ended.
+ * gate_obs (optional, [6][gate_obs_ld], write-only, streaming stores): for the gate h that is next AFTER the step (after the
+ * reset, if there was one), with the post-step (post-reset) attitude R and position p: rows 0..2 = R^T (c_h - p), 3..5 = R^T n_h.
+ * The 14 state rows of a gate handle are bit for bit those of the same handle without a course while no lane resets for a gate
+ * reason.  Kernels (csrc/fpv_gate.hip): a single-step kernel with the rotated traversal (the word row counts among the written
+ * bytes, the obs rows do not), a k-step kernel that holds the word in a register for all k steps and runs the gate logic on every
+ * step (reward and gate_obs only where they are stored), and the word reset that fpv_reset adds on the same stream.  A handle with
+ * stick noise, an object list or a reset source runs its single steps on the k-step kernel (k = 1).
+ * fpv_handle_algorithmic_bytes: 133 + 8 (word read + write) + 24 with gate_obs.
+ * Refused with FPV_EINVAL, by name: fp16 state, Racer mode, a physics table (fpv_set_gates / fpv_set_physics), Kahan rows, the
+ * guidance override, the AoS head, and stick noise together with an object list (at the launch that combines them). */
+#define FPV_MAX_GATES 64
+#define FPV_GATE_FLOATS 16
+enum { FPV_GATE_RECTANGLE = 0, FPV_GATE_CIRCLE = 1, FPV_GATE_HALF_CIRCLE = 2 };
+enum { FPV_GATE_EVENT_NONE = 0, FPV_GATE_EVENT_PASS = 1, FPV_GATE_EVENT_MISS = 2, FPV_GATE_EVENT_FINISH = 3 };
+#define FPV_GATE_WORD_NEXT(w) ((uint32_t)(w) & 0xffu)
+#define FPV_GATE_WORD_EVENT(w) (((uint32_t)(w) >> 8) & 3u)
+#define FPV_GATE_WORD_PASSED(w) ((uint32_t)(w) >> 10)
+#define FPV_GATE_MAX_PASSED 0x3fffffu
+
+typedef struct fpv_gate {            /* what fpv_gates_derive reads: the reference's Gate(position, rotation_matrix, size, shape) */
+    double position[3];
+    double rotation[9];              /* row-major body -> world; orthonormal to 1e-6 */
+    double size;                     /* > 0 */
+    int32_t shape;                   /* FPV_GATE_RECTANGLE / _CIRCLE / _HALF_CIRCLE */
+    int32_t _reserved;
+} fpv_gate_t;
+
+typedef struct fpv_gate_course {
+    uint32_t struct_size;            /* sizeof(fpv_gate_course_t) = fpv_sizeof(5) */
+    int32_t count;                   /* 1..FPV_MAX_GATES */
+    const float* descriptors;        /* [count][FPV_GATE_FLOATS] fp32, 16-byte aligned; DEVICE memory for fpv_set_gates, HOST for fpv_gate_eval */
+    uint32_t* gate_word;             /* [n] DEVICE: the race state, read and written by every step                               */
+    float* gate_obs;                 /* [6][gate_obs_ld] DEVICE or NULL                                                         */
+    int64_t gate_obs_ld;             /* >= n when gate_obs is given                                                             */
+    const uint8_t* gate_start;       /* [n] DEVICE (HOST for fpv_gate_eval) or NULL: the gate a lane starts at after a reset     */
+    int32_t laps;                    /* 0 = endless; > 0: FINISH at laps * count passes (<= FPV_GATE_MAX_PASSED)                  */
+    int32_t miss_is_done;            /* != 0: a MISS ends the episode                                                           */
+    float progress_gain, pass_bonus, finish_bonus, miss_penalty, crash_penalty;
+    float _reserved;
+} fpv_gate_course_t;
+
+/* out_rows[k * FPV_GATE_FLOATS ..] = the descriptor row of gates[k] (host arithmetic only, no device; out_rows is HOST memory).
+ * FPV_EPARAM, naming the gate ("gate <index>: ..."), for a size that is not positive, a rotation that is not orthonormal to
+ * 1e-6, an unknown shape, or a count outside 1..FPV_MAX_GATES. */
+int fpv_gates_derive(int count, const fpv_gate_t* gates, float* out_rows /*[count][FPV_GATE_FLOATS]*/);
+/* Bind a course to a handle (the struct is copied; the device buffers stay the caller's, who keeps them alive and may rewrite the
+ * descriptors between launches - moving gates), or unbind with NULL: the handle then runs exactly the kernels it ran before.
+ * Allocates nothing and never synchronises.  FPV_EINVAL for the refusals above and in a library built without csrc/fpv_gate.hip. */
+int fpv_set_gates(fpv_handle_t h, const fpv_gate_course_t* course);
+/* The kernels' own gate function on the host (no device): for drone i of n, from p_old[i][3], p_new[i][3], q_new[i][4] (wxyz),
+ * physics_done[i] and word_in[i], with a course whose `descriptors` (and `gate_start`) are HOST memory and whose device pointers
+ * are not read: word_out[i], reward[i], done[i] and obs[i][6].  auto_reset != 0 resets the word of a done drone like the kernels
+ * do; its obs is then taken at p_after[i] / q_after[i] (the pose the lane reappears at; NULL: p_new / q_new). */
+int fpv_gate_eval(const fpv_gate_course_t* course, int64_t n, const float* p_old, const float* p_new, const float* q_new,
+                  const uint8_t* physics_done, const uint32_t* word_in, int auto_reset, const float* p_after, const float* q_after,
+                  uint32_t* word_out, float* reward, uint8_t* done, float* obs);
 
 /* Row stride (in floats) to allocate for n drones.  Up to 2^18 drones: n rounded up to 64, padded so that the stride in
  * bytes is at least 1 KiB past a multiple of 8 KiB (strides at or near a multiple of 8 KiB put all 14

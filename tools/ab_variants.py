@@ -19,6 +19,9 @@ VARIANTS = {
     "b64": ["-DFPV_EXP_BLOCK=64"], "b256": ["-DFPV_EXP_BLOCK=256"],       # drones per workgroup (the rotation's block, the XCD's share of a row: 256 B of 2 KiB / 1 KiB of 8 KiB)
     # table loads of the per-drone physics kernels (csrc/fpv_phys.hip; time with --physics): ordinary / with the streaming hint
     "tab": ["-DFPV_EXP_PHYS_TABLE_NT=0"], "tabnt": ["-DFPV_EXP_PHYS_TABLE_NT=1"],
+    # how a lane of the gate kernels reaches its gate's descriptor row (csrc/fpv_gate.hip; time with --gates): per-lane gather from
+    # global memory / the workgroup's LDS copy of the table
+    "gategl": ["-DFPV_EXP_GATE_LDS=0"], "gatelds": ["-DFPV_EXP_GATE_LDS=1"],
     "pre12": ["PRELOAD=12"], "pre16": ["PRELOAD=16"], "pre8": ["PRELOAD=8"],       # kernel-argument dwords preloaded into SGPRs (shipped: 6 = state, ld, action; 12 reaches n_start)
 }
 ap = argparse.ArgumentParser()
@@ -28,6 +31,7 @@ ap.add_argument("--rounds", type=int, default=8)
 ap.add_argument("--only", nargs="*", default=None)
 ap.add_argument("--rotations", nargs="*", type=int, default=[-1], help="fpv_set_rotation values (drones; -1 automatic, 0 plain order) to time every variant at")
 ap.add_argument("--physics", action="store_true", help="bind a randomised physics table (fpv_set_physics) to every variant's handle")
+ap.add_argument("--gates", type=int, default=0, metavar="COUNT", help="bind a round course of COUNT gates with observation rows (fpv_set_gates) to every variant's handle; the lanes' next-gate indices are random")
 ap.add_argument("--out", default=OUT, help="where the variant libraries are built and loaded from")
 ap.add_argument("--states", type=int, default=1, help="time every variant on this many separately allocated state matrices (placement matters beyond the cache)")
 a = ap.parse_args()
@@ -72,6 +76,18 @@ if a.physics:
         L[k].fpv_set_physics.argtypes = [C.c_void_p, C.c_void_p, C.c_int64]
         rc = L[k].fpv_set_physics(H[k], table.data_ptr(), ld); assert rc == 0, L[k].fpv_last_error()
     BYTES = 133 + 4 * (_lib.FPV_PHYS_ROWS - 2)
+if a.gates:
+    from fpyv_amd import gates as G
+    desc = torch.zeros((_lib.FPV_MAX_GATES, _lib.FPV_GATE_FLOATS), device=dev)
+    desc[:a.gates] = torch.from_numpy(G.derive(G.circular_track(a.gates, 8.0, 3.0, height=10.0))).to(dev)
+    word0 = torch.randint(0, a.gates, (n,), dtype=torch.int32, device=dev, generator=torch.Generator(device=dev).manual_seed(5))
+    word, gobs = word0.clone(), torch.zeros((_lib.GATE_OBS_ROWS, ld), device=dev)
+    course = _lib.pack_course(a.gates)
+    course.descriptors, course.gate_word, course.gate_obs, course.gate_obs_ld = desc.data_ptr(), word.data_ptr(), gobs.data_ptr(), ld
+    for k in names:
+        L[k].fpv_set_gates.argtypes = [C.c_void_p, C.c_void_p]
+        rc = L[k].fpv_set_gates(H[k], C.byref(course)); assert rc == 0, L[k].fpv_last_error()
+    BYTES = 133 + 8 + 24
 rew = torch.zeros(n, device=dev); done = torch.zeros(n, dtype=torch.uint8, device=dev)
 if a.states > 1:
     # the same variants on several state matrices of this process, freed and allocated again in between: one line per matrix
@@ -105,6 +121,7 @@ b = _lib.FpvBuffers(); b.state, b.ld, b.reward, b.done = st.data_ptr(), ld, rew.
 b.action = acts.data_ptr()
 def reset(k="base"):
     st.zero_(); st[2] = 10; st[3] = 1; st[6] = 1
+    if a.gates: word.copy_(word0)
 res = {(k, rot): [] for k in names for rot in a.rotations}; fin = {}
 e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
 reps = 8 if n <= (1 << 21) else 16
