@@ -11,7 +11,7 @@
 // as they are, and fpv_hip.hip alone still builds (it reaches the three lookup functions at the end of this file through weak
 // declarations).  Five kernels: the plain single-step kernel, the k-step kernel <NOISE, OBJ> without / with stick noise / with
 // the object list, and the word reset of fpv_reset.  A handle with stick noise, an object list or a reset source runs its single
-// steps on the k-step kernel (k = 1), as reset sources do without a course.
+// steps on the k-step kernel (k = 1), as reset sources do without a course (fpv_hip.hip: plan_launch).
 #include <hip/hip_runtime.h>
 
 #include <stdint.h>

@@ -117,7 +117,7 @@ __global__ __launch_bounds__(kStepBlock) FPV_EXP_STEP_ATTR void fpv_drone_step_k
 //      needs; the reset pose is loaded inside the (rare) reset branch;
 //   2. the remaining steps - the last one, or all of them when reward/done leave per step or episodes are tracked;
 //   3. the stores.
-// SQ: launched only for the X frame without the ground-spring flag and without objects (choose_rollout_kernel):
+// SQ: launched only for the X frame without the ground-spring flag and without objects (plan_launch):
 // the quiet steps use the two-height ground flag (fpv_drone_step_lane<.., SQ = true>).
 template <bool NOISE, bool OBJ, bool KAHAN, bool SQ = false>
 __global__ __launch_bounds__(kStepBlock) void fpv_drone_rollout_kernel(const FpvRollArgs A)
@@ -130,7 +130,7 @@ __global__ __launch_bounds__(kStepBlock) void fpv_drone_rollout_kernel(const Fpv
     FpvDroneState s;
     const int k = A.R.k;
     const bool has_action = !NOISE || A.B.action;
-    // rows only for fpv_step_n; the k = 1 launches a reset-source handle's fpv_step is routed to (choose_kernel) may carry SoA sticks
+    // rows only for fpv_step_n; the k = 1 launches a reset-source handle's fpv_step is routed to (plan_launch) may carry SoA sticks
     float4 a_next = make_float4(0.f, 0.f, 0.f, 0.f);
     if constexpr (SQ) { if (has_action) a_next = ld_action(A.B.action, i); }
     else { if (has_action) a_next = ld_action_any(A.B.action, A.B.action_ld, i); }
@@ -785,6 +785,14 @@ int launch(const char* what, void (*kernel)(P...), dim3 grid, dim3 block, hipStr
     return e == hipSuccess ? FPV_OK : hip_fail(e, what);
 }
 
+// The same for a kernel known by its address, with its arguments as the list of pointers that a graph node takes.
+int launch_args(const char* what, void* kernel, dim3 grid, dim3 block, hipStream_t s, void** args)
+{
+    (void)hipLaunchKernel(kernel, grid, block, args, 0, s);
+    const hipError_t e = hipGetLastError();
+    return e == hipSuccess ? FPV_OK : hip_fail(e, what);
+}
+
 }  // namespace
 
 struct fpv_env {
@@ -831,6 +839,29 @@ extern "C" __attribute__((weak, visibility("hidden"))) void* fpv_gate_roll_kerne
 extern "C" __attribute__((weak, visibility("hidden"))) void* fpv_gate_reset_kernel_fn(void);
 
 namespace {
+
+// the kernel families a call is served by (plan_launch)
+enum Family { kPlain, kFp16, kAos, kRacer, kTable, kGate };
+
+// What a physics table (kTable) and a gate course (kGate) cannot be combined with - what their kernels do not carry, refused by
+// name.  b null: the handle, asked when the feature is bound (fpv_set_physics, fpv_set_gates); else the buffers of a call
+// (check_buffers).  A handle that has the other feature bound is a fp32 drone handle, so the order of the handle's three cannot show.
+int check_combination(const fpv_env* h, Family f, const fpv_buffers_t* b)
+{
+    struct Rule { bool hit; const char* with; };
+    const bool table = f == kTable;
+    const auto refuse = [&](std::initializer_list<Rule> rules) -> int {
+        for (const Rule& r : rules)
+            if (r.hit) return fail(FPV_EINVAL, std::string(table ? "a physics table" : "a gate course") + " cannot be combined with " + r.with);
+        return FPV_OK;
+    };
+    if (!b)
+        return refuse({{h->mode != FPV_MODE_DRONE, "Racer mode"}, {(h->K.flags & FPV_FLAG_FP16_STATE) != 0, "fp16 state (FPV_FLAG_FP16_STATE)"},
+                       table ? Rule{h->gates, "a gate course (fpv_set_gates)"} : Rule{h->phys != nullptr, "a physics table (fpv_set_physics)"}});
+    return refuse({{b->pos_comp != nullptr, "Kahan rows (pos_comp)"}, {b->rotation_override != nullptr, "the guidance override (rotation_override)"},
+                   {b->obs_aos != nullptr, "the AoS head (obs_aos)"},
+                   {!table && (h->K.flags & FPV_FLAG_STICK_NOISE) && b->objects && b->objects->count > 0, "stick noise AND an object list (either one alone is served)"}});
+}
 
 int check_buffers(const fpv_env* h, const fpv_buffers_t* b, bool need_action)  // NOLINT
 {
@@ -896,18 +927,10 @@ int check_buffers(const fpv_env* h, const fpv_buffers_t* b, bool need_action)  /
         if ((uintptr_t)b->reset_pose & 15) return fail(FPV_EALIGN, "reset_pose must be 16-byte aligned");
         if (b->reset_pose && b->ld < h->n) return fail(FPV_EALIGN, "fpv_buffers_t.ld is smaller than the number of drones");
     }
-    if (h->phys) {      // per-drone physics (fpv_abi.h): what the table kernels do not carry is refused by name
-        if (b->pos_comp) return fail(FPV_EINVAL, "a physics table cannot be combined with Kahan rows (pos_comp)");
-        if (b->rotation_override) return fail(FPV_EINVAL, "a physics table cannot be combined with the guidance override (rotation_override)");
-        if (b->obs_aos) return fail(FPV_EINVAL, "a physics table cannot be combined with the AoS head (obs_aos)");
-        if (b->ld != h->phys_ld) return fail(FPV_EALIGN, "the physics table's row stride must be the state's (fpv_buffers_t.ld)");
-    }
-    if (h->gates) {     // a gate course (fpv_abi.h): what the gate kernels do not carry is refused by name
-        if (b->pos_comp) return fail(FPV_EINVAL, "a gate course cannot be combined with Kahan rows (pos_comp)");
-        if (b->rotation_override) return fail(FPV_EINVAL, "a gate course cannot be combined with the guidance override (rotation_override)");
-        if (b->obs_aos) return fail(FPV_EINVAL, "a gate course cannot be combined with the AoS head (obs_aos)");
-        if (noise && b->objects && b->objects->count > 0)
-            return fail(FPV_EINVAL, "a gate course cannot be combined with stick noise AND an object list (either one alone is served)");
+    if (h->phys || h->gates) {
+        const int rc = check_combination(h, h->phys ? kTable : kGate, b);
+        if (rc != FPV_OK) return rc;
+        if (h->phys && b->ld != h->phys_ld) return fail(FPV_EALIGN, "the physics table's row stride must be the state's (fpv_buffers_t.ld)");
     }
     if ((b->ep_return == nullptr) != (b->ep_length == nullptr))
         return fail(FPV_EINVAL, "ep_return and ep_length must be given together");
@@ -972,9 +995,6 @@ struct DeviceGuard {
 // ---- kernel selection: every step kernel has the signature FPV_STEP_PARAMS, every k-step kernel (fpv_step_n) one FpvRollArgs ----
 typedef void (*StepKernel)(float*, const int64_t, const float4*, const int64_t, uint16_t*, const int64_t, const FpvK, const FpvBufD);
 typedef void (*RollKernel)(const FpvRollArgs);
-typedef void (*PhysRollKernel)(const FpvRollPhysArgs);
-typedef void (*GateStepKernel)(float*, const int64_t, const float4*, const int64_t, uint32_t*, const int64_t, const FpvK, const FpvBufD, const FpvGateArgs);
-typedef void (*GateRollKernel)(const FpvRollGateArgs);
 typedef void (*GateResetKernel)(uint32_t*, const uint8_t*, const uint8_t*, const uint32_t, const int64_t);
 // blocks of one single-step launch: n's, in whole rounds of the eight XCDs - every single-step kernel (drone, fp16 state, AoS head,
 // Racer) reads n and the start block from one argument, and FPV_STEP_INDEX computes the same number from n
@@ -1003,6 +1023,7 @@ const StepKernel kRacerStep[2][2] = {{fpv_racer_step_kernel<false, false>, fpv_r
 const RollKernel kRacerRoll[2][2] = {{fpv_racer_rollout_kernel<false, false>, fpv_racer_rollout_kernel<false, true>},
                                      {fpv_racer_rollout_kernel<true, false>, fpv_racer_rollout_kernel<true, true>}};
 
+// ---- the launch plan: which kernel serves a call, and on which path, is decided in plan_launch and nowhere else ----
 // Reset sources (fpv_abi.h: the reset-pose table, FPV_FLAG_RESET_JITTER) live in the rare reset branch of the kernels that are
 // NOT on the headline path: the non-SQ k-step kernels, the fp16 k-step kernel, the AoS-head kernel and the reset kernel.  The
 // plain and fp16 single-step kernels and the SQ k-step kernel stay exactly as they were (tests/test_isa_claims.py pins them), so
@@ -1015,103 +1036,123 @@ const RollKernel kRacerRoll[2][2] = {{fpv_racer_rollout_kernel<false, false>, fp
 //   - fpv_step_n never picks SQ; fpv_rollout_graph issues the launches instead of replaying them (the jitter needs the step
 //     index of every launch).
 // Cost: DESIGN.md "Reset sources".
-bool has_reset_source(const fpv_env* h, const FpvBufD& d)
+// A physics table and a gate course follow the same rule with the kernels of fpv_phys.hip and fpv_gate.hip, whose k-step kernels
+// carry the branch; a course with stick noise or an object list has no single-step kernel and takes the k = 1 route as well.
+// A graph replays frozen kernel arguments, but stick noise, the fp16 rounding and the jitter are keyed by the per-launch step
+// index: fpv_rollout_graph hands such a call, and every call whose single steps are the k-step kernel's, to fpv_step_n - the
+// same k steps bit for bit, and cheaper than the replay - or to fpv_rollout when the AoS head is written (fpv_step_n writes none).
+enum GraphRoute { kReplay, kToStepN, kToRollout };      // what fpv_rollout_graph does with a call
+struct Plan {
+    Family family;
+    void* step;             // the single-step kernel (FPV_STEP_PARAMS; kGate: then one FpvGateArgs), or null: a single step is one step (k = 1) of `roll`, not rotated
+    void* roll;             // the k-step kernel, of one FpvRollArgs (kTable: FpvRollPhysArgs, kGate: FpvRollGateArgs)
+    bool ground = false;    // kTable: the launch loads the two ground rows
+    GraphRoute graph = kReplay;
+};
+
+// a kernel's address as a launch and a graph node take it - the one cast (the tables above stay typed by signature)
+template <class... P> void* entry(void (*kernel)(P...)) { return reinterpret_cast<void*>(kernel); }
+
+Plan plan_launch(const fpv_env* h, const FpvBufD& d)
 {
-    return h->mode == FPV_MODE_DRONE && (d.reset_pose != nullptr || (h->K.flags & FPV_FLAG_RESET_JITTER) != 0);
+    const bool noise = (h->K.flags & FPV_FLAG_STICK_NOISE) != 0, fp16 = (h->K.flags & FPV_FLAG_FP16_STATE) != 0;
+    const bool obj = d.objs.count > 0, kahan = d.pos_comp != nullptr, aos = d.obs_aos != nullptr, ground = (h->K.flags & FPV_FLAG_GROUND) != 0;
+    const bool wide = h->K.r_wide != 0, pidv = h->K.r_pid_variant != 0;
+    const bool reset = h->mode == FPV_MODE_DRONE && (d.reset_pose != nullptr || (h->K.flags & FPV_FLAG_RESET_JITTER) != 0);
+    // the SQ k-step bodies: X frame, no ground springs, no object list - and no reset source, which they do not carry
+    const bool sq = !obj && h->K.motor_square && !ground && !reset;
+    Plan p;
+    // a course and a table: [stick noise][object list] (a course with both is refused, check_combination); a table launch loads
+    // the two ground rows when something reads them; the guidance override has the plain or the object-list kernel (check_buffers)
+    if (h->gates) p = {kGate, noise || obj ? nullptr : fpv_gate_step_kernel(), fpv_gate_roll_kernel(noise, obj)};
+    else if (h->phys) p = {kTable, fpv_phys_step_kernel(noise, obj), fpv_phys_roll_kernel(noise, obj), ground || obj};
+    else if (h->mode != FPV_MODE_DRONE) p = {kRacer, entry(kRacerStep[wide][pidv]), entry(kRacerRoll[wide][pidv])};
+    else if (fp16) p = {kFp16, entry(fpv_drone_step_h_kernel), entry(fpv_drone_rollout_h_kernel)};
+    else p = {aos ? kAos : kPlain, entry(aos ? fpv_drone_step_aos_kernel : d.rot_over ? kDroneStepOverride[obj] : kDroneStep[noise][obj][kahan]),
+              entry(sq ? kDroneRollSq[noise][kahan] : kDroneRoll[noise][obj][kahan])};
+    if (reset && !aos) p.step = nullptr;
+    p.graph = noise || fp16 || !p.step ? kToStepN : reset ? kToRollout : kReplay;
+    return p;
 }
 
-// Per-drone physics: does a launch with these buffers load the two ground rows (and how many rows that makes)?
-bool phys_ground(const fpv_env* h, const FpvBufD& d) { return (h->K.flags & FPV_FLAG_GROUND) != 0 || d.objs.count > 0; }
-int phys_rows(const fpv_env* h, const FpvBufD& d) { return phys_ground(h, d) ? FPV_PHYS_ROWS : FPV_PHYS_ROWS - 2; }
-
-RollKernel choose_rollout_kernel(const fpv_env* h, const FpvBufD& d)
+// an accepted launch of k steps: the step index advances (a refused launch leaves it where it was) and a table handle remembers
+// the rows it loaded
+void launched(fpv_env* h, const Plan& p, int k)
 {
-    if (h->mode != FPV_MODE_DRONE) return kRacerRoll[h->K.r_wide != 0][h->K.r_pid_variant != 0];
-    if (h->K.flags & FPV_FLAG_FP16_STATE) return fpv_drone_rollout_h_kernel;
-    const bool noise = (h->K.flags & FPV_FLAG_STICK_NOISE) != 0, obj = d.objs.count > 0, kahan = d.pos_comp != nullptr;
-    const bool sq = !obj && h->K.motor_square && !(h->K.flags & FPV_FLAG_GROUND)      // X frame, no ground springs
-                    && !has_reset_source(h, d);                                          // (the SQ bodies carry no reset source)
-    return sq ? kDroneRollSq[noise][kahan] : kDroneRoll[noise][obj][kahan];
+    h->launches += (uint64_t)k;
+    if (p.family == kTable) h->phys_rows_last = p.ground ? FPV_PHYS_ROWS : FPV_PHYS_ROWS - 2;
 }
 
-// the single-step kernel (FPV_STEP_PARAMS) of a launch, or null: the launch is one step of the k-step kernel (reset sources, above)
-StepKernel choose_kernel(const fpv_env* h, const FpvBufD& d)
+// one launch of the k-step kernel over the handle's drones: R.k steps from the handle's step index
+int launch_roll(fpv_env* h, const Plan& p, const FpvBufD& d, const FpvRoll& R, hipStream_t s, const char* what)
 {
-    if (has_reset_source(h, d) && !d.obs_aos) return nullptr;      // routed around the pinned single-step kernels (see has_reset_source)
-    // a gate course: fpv_gate.hip's plain single-step kernel (launch_step / GraphNode pass it the ninth argument); with stick noise
-    // or an object list the k-step kernel with k = 1, like a reset source
-    if (h->gates)
-        return ((h->K.flags & FPV_FLAG_STICK_NOISE) || d.objs.count > 0) ? nullptr : reinterpret_cast<StepKernel>(fpv_gate_step_kernel());
-    // a physics table: fpv_phys.hip's single-step kernel - the same argument layout, the table base in the state_h slot (step_slot5)
-    if (h->phys) return reinterpret_cast<StepKernel>(fpv_phys_step_kernel((h->K.flags & FPV_FLAG_STICK_NOISE) != 0, d.objs.count > 0));
-    if (h->mode != FPV_MODE_DRONE) return kRacerStep[h->K.r_wide != 0][h->K.r_pid_variant != 0];
-    if (h->K.flags & FPV_FLAG_FP16_STATE) return fpv_drone_step_h_kernel;
-    if (d.obs_aos) return fpv_drone_step_aos_kernel;
-    const bool noise = (h->K.flags & FPV_FLAG_STICK_NOISE) != 0, obj = d.objs.count > 0, kahan = d.pos_comp != nullptr;
-    return d.rot_over ? kDroneStepOverride[obj] : kDroneStep[noise][obj][kahan];
-}
-
-// one launch of the k-step kernel over the handle's drones, R.k steps from the step index d.step; an accepted launch advances
-// the handle's step index by R.k
-// the fifth and sixth leading scalars of a single-step launch: state_h - or the physics table, whose kernels read no fp16 state -
-// and n | start block << 32, with kPhysGroundBit when a table launch loads the ground rows
-uint16_t* step_slot5(const fpv_env* h, const FpvBufD& d)
-{
-    if (h->gates) return reinterpret_cast<uint16_t*>(h->ga.word);
-    return h->phys ? reinterpret_cast<uint16_t*>(const_cast<float*>(h->phys)) : d.state_h;
-}
-int64_t step_n_start(const fpv_env* h, const FpvBufD& d, int64_t start)
-{
-    return h->n | (start << 32) | (h->phys && phys_ground(h, d) ? kPhysGroundBit : 0);
-}
-
-int launch_roll(fpv_env* h, const FpvBufD& d, const FpvRoll& R, hipStream_t s, const char* what)
-{
+    FpvRollArgs a = {h->K, d, h->n, R};
+    a.B.step = h->launches;
     FpvRollPhysArgs pa;
-    memset(&pa, 0, sizeof(pa));
-    FpvRollArgs& args = pa.A;
-    args.K = h->K; args.B = d; args.n = h->n; args.R = R;
-    int rc;
-    if (h->gates) {
-        FpvRollGateArgs ga;
-        memset(&ga, 0, sizeof(ga));
-        ga.A = args; ga.G = h->ga;
-        rc = launch(what, reinterpret_cast<GateRollKernel>(fpv_gate_roll_kernel((h->K.flags & FPV_FLAG_STICK_NOISE) != 0, d.objs.count > 0)),
-                    blocks_for(h->n, kStepBlock), dim3(kStepBlock), s, ga);
-    } else if (h->phys) {
-        pa.phys = h->phys;
-        pa.ground = phys_ground(h, d) ? 1 : 0;
-        h->phys_rows_last = phys_rows(h, d);
-        rc = launch(what, reinterpret_cast<PhysRollKernel>(fpv_phys_roll_kernel((h->K.flags & FPV_FLAG_STICK_NOISE) != 0, d.objs.count > 0)),
-                    blocks_for(h->n, kStepBlock), dim3(kStepBlock), s, pa);
-    } else {
-        rc = launch(what, choose_rollout_kernel(h, d), blocks_for(h->n, kStepBlock), dim3(kStepBlock), s, args);
-    }
-    if (rc == FPV_OK) h->launches += (uint64_t)R.k;
+    FpvRollGateArgs ga;
+    void* arg = &a;
+    if (p.family == kTable) { pa = {a, h->phys, p.ground ? 1 : 0, 0}; arg = &pa; }
+    if (p.family == kGate) { ga = {a, h->ga}; arg = &ga; }
+    const int rc = launch_args(what, p.roll, blocks_for(h->n, kStepBlock), dim3(kStepBlock), s, &arg);
+    if (rc == FPV_OK) launched(h, p, R.k);
     return rc;
 }
 
+// The arguments of one single-step launch, filled in place - for the direct launch (launch_step) and for the kernel node of a
+// graph alike: FPV_STEP_PARAMS' eight and the gate kernel's ninth (the other kernels do not read it).  The fifth is state_h - or
+// the physics table or the gate word, whose kernels read no fp16 state -, the sixth n | start block << 32, with kPhysGroundBit
+// when a table launch loads the ground rows.  np.kernelParams points at this object's own members, which hipLaunchKernel /
+// hipGraphAddKernelNode / hipGraphExecKernelNodeSetParams copy - so it is used where it is built and never copied.
+struct StepLaunch {
+    FpvBufD d;
+    FpvK K;
+    int64_t n_start;
+    void* slot5;
+    FpvGateArgs ga;
+    void* args[9];
+    hipKernelNodeParams np;
+    StepLaunch(const fpv_env* h, const Plan& p, const FpvBufD& dt, int64_t start)
+        : d(dt), K(h->K), n_start(h->n | (start << 32) | (p.ground ? kPhysGroundBit : 0)),
+          slot5(p.family == kGate ? (void*)h->ga.word : p.family == kTable ? (void*)const_cast<float*>(h->phys) : (void*)dt.state_h),
+          ga(h->ga), args{&d.state, &d.ld, &d.action, &d.action_ld, &slot5, &n_start, &K, &d, &ga}
+    {
+        memset(&np, 0, sizeof(np));
+        np.func = p.step; np.kernelParams = args;
+        np.gridDim = dim3((unsigned)step_grid(h->n)); np.blockDim = dim3(kStepBlock);
+    }
+    StepLaunch(const StepLaunch&) = delete;
+    StepLaunch& operator=(const StepLaunch&) = delete;
+};
+
 int64_t rotation_blocks(const fpv_env* h, const FpvBufD* d);      // below, with the cache sizes
 
-int launch_step(fpv_env* h, const FpvBufD& d_in, hipStream_t s)
+// one single step from the handle's step index; a step of the k-step kernel returns before the rotation is touched
+// (fpv_get_rotation reports what the last rotating launch set)
+int launch_step(fpv_env* h, const Plan& p, const FpvBufD& d, hipStream_t s)
 {
-    FpvBufD d = d_in;
-    d.step = h->launches;
-    const StepKernel f = choose_kernel(h, d);
     // one step of the k-step kernel: reward / done / done_bits / episode sums leave after it, as after a single step
-    if (!f) return launch_roll(h, d, FpvRoll{1, 0, 0, 0, 0}, s, "step kernel launch");
+    if (!p.step) return launch_roll(h, p, d, FpvRoll{1, 0, 0, 0, 0}, s, "step kernel launch");
     const int64_t nblk = step_grid(h->n);
     h->rot_blocks = rotation_blocks(h, &d);
     const int64_t start = h->rot_blocks > 0 ? h->start_block % nblk : 0;
-    if (h->phys) h->phys_rows_last = phys_rows(h, d);
-    const int rc = h->gates ? launch("step kernel launch", reinterpret_cast<GateStepKernel>(fpv_gate_step_kernel()), dim3((unsigned)nblk), dim3(kStepBlock), s, d.state, d.ld,
-                                     d.action, d.action_ld, h->ga.word, step_n_start(h, d, start), h->K, d, h->ga)
-                            : launch("step kernel launch", f, dim3((unsigned)nblk), dim3(kStepBlock), s, d.state, d.ld, d.action, d.action_ld,
-                                     step_slot5(h, d), step_n_start(h, d, start), h->K, d);
+    StepLaunch L(h, p, d, start);
+    L.d.step = h->launches;
+    const int rc = launch_args("step kernel launch", L.np.func, L.np.gridDim, L.np.blockDim, s, L.np.kernelParams);
     if (rc != FPV_OK) return rc;
-    ++h->launches;                     // a refused launch leaves the step index where it was
+    launched(h, p, 1);
     if (h->rot_blocks > 0) h->start_block = (start + nblk - h->rot_blocks % nblk) % nblk;
     return FPV_OK;
+}
+
+// SHAPE of a graph: what patching its nodes cannot change - the kernel, the grid, the number of nodes - and every non-pointer
+// argument of its launches, the handle's table and course with them (each zero-padded where it was filled).  Everything else in
+// the view is a buffer address.  (The rounding seed and the jitter constants are arguments and so in the key, though no kernel a
+// graph replays reads them: a changed seed on a handle without fp16 state rebuilds the graph where a patch would have done.)
+template <class... T> std::string bytes_of(const T&... v)
+{
+    std::string s;
+    (s.append(reinterpret_cast<const char*>(&v), sizeof(v)), ...);
+    return s;
 }
 
 // MI355X: 256 MiB Infinity Cache (memory-side, shared by the eight XCDs) behind eight L2s of 4 MiB, one per XCD
@@ -1266,33 +1307,6 @@ double l2_set_overflow(int64_t stride_bytes, int64_t blocks)
     return worst;
 }
 
-// The kernel node of step t of a graph, filled in place: np.kernelParams points at this object's own d, n_start and K, which
-// hipGraphAddKernelNode / hipGraphExecKernelNodeSetParams copy - so it is used where it is built and never copied.  Node t has
-// launch_step's rotation, counted from the first node (a replay begins where the previous one began: one launch in k starts on
-// cold rows).
-struct GraphNode {
-    FpvBufD d;
-    FpvK K;
-    int64_t n_start;
-    uint16_t* slot5;
-    FpvGateArgs ga;         // the ninth parameter of the gate kernel (the others have eight and do not read it)
-    void* args[9];
-    hipKernelNodeParams np;
-    GraphNode(const fpv_env* h, const FpvBufD& dt, int t)
-        : d(dt), K(h->K), slot5(step_slot5(h, dt)), ga(h->ga), args{&d.state, &d.ld, &d.action, &d.action_ld, &slot5, &n_start, &K, &d, &ga}
-    {
-        const int64_t nblk = step_grid(h->n), rot = rotation_blocks(h, &d);
-        const int64_t start = rot > 0 ? (int64_t)(((uint64_t)t * (uint64_t)(nblk - rot % nblk)) % (uint64_t)nblk) : 0;
-        n_start = step_n_start(h, d, start);
-        memset(&np, 0, sizeof(np));
-        np.func = reinterpret_cast<void*>(choose_kernel(h, d));
-        np.gridDim = dim3((unsigned)nblk); np.blockDim = dim3(kStepBlock);
-        np.kernelParams = args;
-    }
-    GraphNode(const GraphNode&) = delete;
-    GraphNode& operator=(const GraphNode&) = delete;
-};
-
 // The row stride that needs no model of the caches: n rounded up to 64 floats and kept at least 1 KiB past a multiple of 8 KiB.
 // 14 rows whose stride is (nearly) a multiple of 8 KiB land on the same HBM channel/bank set: measured at 2^20 drones, stride mod
 // 8 KiB = 0 costs 6-9 %, 256-448 B still 2-3 %, 1-4 KiB nothing.
@@ -1401,9 +1415,8 @@ int fpv_set_physics(fpv_handle_t h, const float* table, int64_t ld)
         return fail(FPV_EINVAL, "per-drone physics is not in this build (the library was linked without csrc/fpv_phys.hip)");
     if (!h) return fail(FPV_EINVAL, "null handle");
     if (table) {
-        if (h->gates) return fail(FPV_EINVAL, "a physics table cannot be combined with a gate course (fpv_set_gates)");
-        if (h->mode != FPV_MODE_DRONE) return fail(FPV_EINVAL, "a physics table cannot be combined with Racer mode");
-        if (h->K.flags & FPV_FLAG_FP16_STATE) return fail(FPV_EINVAL, "a physics table cannot be combined with fp16 state (FPV_FLAG_FP16_STATE)");
+        const int rc = check_combination(h, kTable, nullptr);
+        if (rc != FPV_OK) return rc;
         if ((uintptr_t)table & 15) return fail(FPV_EALIGN, "the physics table must be 16-byte aligned");
         if (ld < h->n) return fail(FPV_EALIGN, "the physics table's ld is smaller than the number of drones");
         if (ld % 4) return fail(FPV_EALIGN, "the physics table's ld must be a multiple of 4 floats");
@@ -1469,11 +1482,9 @@ int fpv_set_gates(fpv_handle_t h, const fpv_gate_course_t* c)
     }
     FpvGateArgs a;
     memset(&a, 0, sizeof(a));          // padding bytes are part of the graph-cache key
-    const int rc = gate_constants(c, &a.K);
+    int rc = gate_constants(c, &a.K);
+    if (rc == FPV_OK) rc = check_combination(h, kGate, nullptr);
     if (rc != FPV_OK) return rc;
-    if (h->mode != FPV_MODE_DRONE) return fail(FPV_EINVAL, "a gate course cannot be combined with Racer mode");
-    if (h->K.flags & FPV_FLAG_FP16_STATE) return fail(FPV_EINVAL, "a gate course cannot be combined with fp16 state (FPV_FLAG_FP16_STATE)");
-    if (h->phys) return fail(FPV_EINVAL, "a gate course cannot be combined with a physics table (fpv_set_physics)");
     if (!c->descriptors || !c->gate_word) return fail(FPV_EINVAL, "fpv_gate_course_t.descriptors and gate_word must be given");
     if ((uintptr_t)c->descriptors & 15) return fail(FPV_EALIGN, "the gate descriptors must be 16-byte aligned");
     if (((uintptr_t)c->gate_word & 3) || ((uintptr_t)c->gate_obs & 3)) return fail(FPV_EALIGN, "gate_word and gate_obs must be 4-byte aligned");
@@ -1698,7 +1709,8 @@ int fpv_step(fpv_handle_t h, const fpv_buffers_t* b, void* stream)
     if (rc != FPV_OK) return rc;
     const DeviceGuard dev(h->device);
     if (dev.rc != FPV_OK) return dev.rc;
-    return launch_step(h, to_device_view(h, b), (hipStream_t)stream);
+    const FpvBufD d = to_device_view(h, b);
+    return launch_step(h, plan_launch(h, d), d, (hipStream_t)stream);
 }
 
 namespace {
@@ -1738,8 +1750,9 @@ int fpv_rollout(fpv_handle_t h, const fpv_buffers_t* b, int k, int64_t action_st
     const DeviceGuard dev(h->device);
     if (dev.rc != FPV_OK) return dev.rc;
     const FpvBufD d0 = to_device_view(h, b);
+    const Plan p = plan_launch(h, d0);
     for (int t = 0; t < k; ++t)
-        if ((rc = launch_step(h, graph_step_view(b, d0, t, action_stride, out_stride), (hipStream_t)stream)) != FPV_OK) return rc;
+        if ((rc = launch_step(h, p, graph_step_view(b, d0, t, action_stride, out_stride), (hipStream_t)stream)) != FPV_OK) return rc;
     return FPV_OK;
 }
 
@@ -1788,9 +1801,8 @@ int fpv_step_n(fpv_handle_t h, const fpv_buffers_t* b, int k, int64_t action_str
     if (b->rotation_override) return fail(FPV_EINVAL, "the guidance override is a per-step input: use fpv_step");
     const DeviceGuard dev(h->device);
     if (dev.rc != FPV_OK) return dev.rc;
-    FpvBufD d = to_device_view(h, b);
-    d.step = h->launches;
-    return launch_roll(h, d, FpvRoll{k, 0, action_stride, out_stride, b->done_bits_stride}, (hipStream_t)stream, "k-step kernel launch");
+    const FpvBufD d = to_device_view(h, b);
+    return launch_roll(h, plan_launch(h, d), d, FpvRoll{k, 0, action_stride, out_stride, b->done_bits_stride}, (hipStream_t)stream, "k-step kernel launch");
 }
 
 int fpv_rollout_graph(fpv_handle_t h, const fpv_buffers_t* b, int k, int64_t action_stride, int64_t out_stride,
@@ -1801,39 +1813,27 @@ int fpv_rollout_graph(fpv_handle_t h, const fpv_buffers_t* b, int k, int64_t act
     if (k <= 0) return fail(FPV_EINVAL, "k must be positive");
     if (action_stride % 4) return fail(FPV_EALIGN, "action_stride must keep 16-byte alignment");
     if (b->rotation_override) return fail(FPV_EINVAL, "the guidance override is a per-step input: use fpv_step");
-    // a graph replays frozen kernel arguments, but stick noise and the fp16 rounding are keyed by the per-launch step
-    // index: such handles take the k-step kernel instead - the same k steps bit for bit, and cheaper than the replay
-    if (h->K.flags & (FPV_FLAG_STICK_NOISE | FPV_FLAG_FP16_STATE)) return fpv_step_n(h, b, k, action_stride, out_stride, stream);
-    // the same for a reset source (the jitter is keyed by the step index; the table needs a routed kernel): the k-step kernel, or
-    // the issued launches when the AoS head is written (fpv_step_n writes none)
-    if (b->reset_pose || (h->K.flags & FPV_FLAG_RESET_JITTER))
-        return b->obs_aos ? fpv_rollout(h, b, k, action_stride, out_stride, stream) : fpv_step_n(h, b, k, action_stride, out_stride, stream);
-    // and for a gate course with an object list, whose single steps are the k-step kernel's
-    if (h->gates && b->objects && b->objects->count > 0) return fpv_step_n(h, b, k, action_stride, out_stride, stream);
+    const FpvBufD d0 = to_device_view(h, b);
+    const Plan p = plan_launch(h, d0);
+    // not replayed (plan_launch says why): the call is the other entry point's, with that one's own refusals and device guard
+    if (p.graph == kToStepN) return fpv_step_n(h, b, k, action_stride, out_stride, stream);
+    if (p.graph == kToRollout) return fpv_rollout(h, b, k, action_stride, out_stride, stream);
     const DeviceGuard dev(h->device);
     if (dev.rc != FPV_OK) return dev.rc;
-    const FpvBufD d0 = to_device_view(h, b);
-    // SHAPE of the graph: everything that selects kernels, grids and non-pointer arguments
-    const StepKernel f0 = choose_kernel(h, d0);
-    std::string shape(reinterpret_cast<const char*>(&h->K), sizeof(h->K));
-    const int64_t meta[7] = {k, action_stride, out_stride, h->n, b->ld, b->action_ld, b->done_bits_stride};
-    shape.append(reinterpret_cast<const char*>(meta), sizeof(meta));
-    shape.append(reinterpret_cast<const char*>(&f0), sizeof(f0));
-    shape.append(reinterpret_cast<const char*>(&d0.objs), sizeof(d0.objs));
-    const float wind[3] = {d0.wx, d0.wy, d0.wz};
-    shape.append(reinterpret_cast<const char*>(wind), sizeof(wind));
-    const int64_t table[2] = {(int64_t)(uintptr_t)h->phys, h->phys_ld};              // a bound physics table (fpv_set_physics)
-    shape.append(reinterpret_cast<const char*>(table), sizeof(table));
-    if (h->gates) shape.append(reinterpret_cast<const char*>(&h->ga), sizeof(h->ga));           // a bound course (fpv_set_gates; zero-padded there)
-    // everything else in the view is a buffer address
-    const std::string ptrs(reinterpret_cast<const char*>(&d0), sizeof(d0));
+    const std::string shape = bytes_of(p.step, step_grid(h->n), h->n, p.ground, FpvRoll{k, 0, action_stride, out_stride, b->done_bits_stride}, h->K, d0.ld,
+                                       d0.action_ld, d0.wx, d0.wy, d0.wz, d0.seed, d0.objs, d0.rj, h->phys, h->phys_ld, h->ga);
+    const std::string ptrs = bytes_of(d0);
+    // node t starts where launch_step would after t launches, counted from the first node (a replay begins where the previous one
+    // began: one launch in k starts on cold rows)
+    const int64_t nblk = step_grid(h->n), rot = rotation_blocks(h, &d0);
+    const auto start = [&](int t) { return rot > 0 ? (int64_t)(((uint64_t)t * (uint64_t)(nblk - rot % nblk)) % (uint64_t)nblk) : 0; };
     if (!h->graph_exec || shape != h->graph_shape_key) {
         drop_graph(h);
         hipError_t e = hipGraphCreate(&h->graph, 0);
         if (e != hipSuccess) { drop_graph(h); return hip_fail(e, "hipGraphCreate"); }
         hipGraphNode_t prev = nullptr;
         for (int t = 0; t < k; ++t) {
-            const GraphNode g(h, graph_step_view(b, d0, t, action_stride, out_stride), t);
+            const StepLaunch g(h, p, graph_step_view(b, d0, t, action_stride, out_stride), start(t));
             hipGraphNode_t node;
             e = hipGraphAddKernelNode(&node, h->graph, prev ? &prev : nullptr, prev ? 1 : 0, &g.np);
             if (e != hipSuccess) { drop_graph(h); return hip_fail(e, "hipGraphAddKernelNode"); }
@@ -1847,7 +1847,7 @@ int fpv_rollout_graph(fpv_handle_t h, const fpv_buffers_t* b, int k, int64_t act
     } else if (ptrs != h->graph_ptr_key) {
         // same shape, new buffers (e.g. a fresh actions tensor every call): patch the node arguments
         for (int t = 0; t < k; ++t) {
-            const GraphNode g(h, graph_step_view(b, d0, t, action_stride, out_stride), t);
+            const StepLaunch g(h, p, graph_step_view(b, d0, t, action_stride, out_stride), start(t));
             const hipError_t e = hipGraphExecKernelNodeSetParams(h->graph_exec, h->graph_nodes[(size_t)t], &g.np);
             if (e != hipSuccess) { drop_graph(h); return hip_fail(e, "hipGraphExecKernelNodeSetParams"); }
         }
@@ -1855,8 +1855,7 @@ int fpv_rollout_graph(fpv_handle_t h, const fpv_buffers_t* b, int k, int64_t act
     }
     const hipError_t e = hipGraphLaunch(h->graph_exec, (hipStream_t)stream);
     if (e != hipSuccess) return hip_fail(e, "hipGraphLaunch");
-    h->launches += (uint64_t)k;
-    if (h->phys) h->phys_rows_last = phys_rows(h, d0);
+    launched(h, p, k);
     return FPV_OK;
 }
 

@@ -370,14 +370,14 @@ __device__ __forceinline__ void apply_reset_source_k(uint32_t i, uint64_t t, Fpv
     s.q.w = pose[6]; s.q.x = pose[7]; s.q.y = pose[8]; s.q.z = pose[9];
 }
 
-// ---- per-drone physics (csrc/fpv_phys.hip; launched from fpv_hip.hip) ----
+// ---- per-drone physics (csrc/fpv_phys.hip; launched from fpv_hip.hip: plan_launch picks the kernel, StepLaunch / launch_roll fill these) ----
 // k-step kernels: the arguments of fpv_drone_rollout_kernel first (the views above read them at the same offsets), then the table
 struct FpvRollPhysArgs { FpvRollArgs A; const float* phys; int32_t ground; int32_t pad; };
 // single-step kernels: n <= 2^28, so bit 31 of n_start's low word is free - "this launch loads the two ground rows", decided on
 // the host and read from a preloaded SGPR: no scalar load stands between the wave's start and its table loads
 constexpr int64_t kPhysGroundBit = (int64_t)1 << 31;
 
-// ---- gate courses (csrc/fpv_gate.hip; launched from fpv_hip.hip) ----
+// ---- gate courses (csrc/fpv_gate.hip; launched from fpv_hip.hip in the same way) ----
 // what fpv_set_gates binds, as the kernels read it: the descriptor table, the word row, the optional observation rows and start
 // gates, the course's uniform constants.  The single-step kernel takes FPV_STEP_PARAMS with the word base in the state_h slot - a
 // gate handle has no fp16 state - and this struct as a ninth parameter; the k-step kernels take one FpvRollGateArgs, the

@@ -77,8 +77,8 @@ struct FpvKLane {
 // the table loads in its load block.  The leading scalars are FPV_STEP_PARAMS' with the table base in the slot of state_h - a
 // table handle has no fp16 state -, so all six are preloaded into SGPRs and the 11 or 13 table loads go out with the 14 state
 // loads, before anything has to be waited for; whether the two ground rows are among them is bit 31 of n_start's low word
-// (kPhysGroundBit), decided by the host, so that test reads a preloaded SGPR too.  The traversal rotates like every single-step
-// kernel's (launch_step / rotation_blocks: the table is only read and does not count among the written bytes).
+// (kPhysGroundBit), decided by the host (plan_launch), so that test reads a preloaded SGPR too.  The traversal rotates like every single-step
+// kernel's (fpv_hip.hip: launch_step / rotation_blocks; the table is only read and does not count among the written bytes).
 template <bool NOISE, bool OBJ>
 __global__ __launch_bounds__(kStepBlock) void fpv_drone_step_phys_kernel(float* __restrict__ a_state, const int64_t a_ld,
                                                                          const float4* __restrict__ a_action, const int64_t a_action_ld,

@@ -345,3 +345,32 @@ def test_unbinding_and_moving_gates():
     _check_now(c, m, 74, "moved gates, single steps")
     c.rollout(a[75:120])
     _check_now(c, m, 119, "moved gates, fpv_step_n")
+
+
+# ---- every course row on every multi-step call -------------------------------------------------------------------------------
+@pytest.mark.parametrize("how", ["rollout", "step_n", "graph"])
+@pytest.mark.parametrize("row", ["plain", "objects", "noise", "reset_pose"])
+def test_course_rows_on_the_multi_step_calls_equal_single_steps(row, how):
+    """A course alone, with an object list, with stick noise and with a reset-pose table under a ceiling that resets lanes at
+    once: fpv_rollout, fpv_step_n and fpv_rollout_graph (with an object list, stick noise or a reset source handed on to
+    fpv_step_n) leave the bits of the same handle type stepped with fpv_step - 1000 drones, two calls of k = 5."""
+    k = 5
+    p = load_params(fps=1000, ceiling=10.2) if row == "reset_pose" else load_params(fps=1000)
+    kw = dict(objects={}, plain={}, noise=dict(stick_noise=True, noise_seed=11), reset_pose=dict(auto_reset=True, per_drone_reset_pose=True))[row]
+    objects = G10_OBJECTS if row == "objects" else None
+    pos, vel, ypr = gc.starts()
+    a = torch.from_numpy(gc.acts()[:2 * k]).to(DEV)
+    one, many = (DroneBatch(p, N, device=DEV, gates=gc.course(), **kw) for _ in range(2))
+    for b in (one, many):
+        b.reset(position=pos, velocity=vel, ypr=ypr)
+    resets = 0
+    for t in range(2 * k):
+        one.step(a[t], object_list=objects or (), return_imu=False)
+        resets += int(one.done.sum())
+    for c in range(2):
+        many.rollout(a[c * k:(c + 1) * k], object_list=objects, **dict(rollout=dict(fused=False), step_n={}, graph=dict(graph=True))[how])
+    assert one.step_counter() == many.step_counter() == 2 * k
+    for name in ("state", "gate_word", "gate_obs_rows", "reward", "done", "noise_state"):
+        x, y = getattr(one, name), getattr(many, name)
+        assert (x is None and y is None) or torch.equal(x.view(torch.uint8), y.view(torch.uint8)), name
+    assert row != "reset_pose" or resets > N, "the ceiling must reset lanes in these steps"

@@ -242,3 +242,39 @@ def test_config2_full_size_1000_steps_fused_noise_vs_oracle(params_1k):
     torch.cuda.synchronize()
     assert torch.equal(fused.state, env.state) and torch.equal(fused.noise_state, env.noise_state)
     assert torch.equal(fused.action_out, env.action_out) and torch.equal(fused.reward, env.reward)
+
+
+@pytest.mark.parametrize("how", ["rollout", "step_n", "graph"])
+@pytest.mark.parametrize("row", ["racer", "racer_written", "racer_cpid", "ground"])
+def test_racer_and_ground_rows_on_the_multi_step_calls_equal_single_steps(params_1k, row, how):
+    """The three Racer instantiations (base, wide, PID variant) and a drone handle with FPV_FLAG_GROUND: fpv_rollout, fpv_step_n
+    and fpv_rollout_graph leave the bits of the same handle type stepped with fpv_step - 1000 drones, two calls of k = 5 (the
+    second graph call patches the nodes: new action addresses)."""
+    from fpyv_amd.env import DroneBatch, RacerBatch
+    n, k = 1000, 5
+    rng = np.random.default_rng(13)
+    if row == "ground":
+        p = params_1k.replace(ground=True, init_position=np.array([0.0, 0.0, 0.003]), init_velocity=np.array([1.0, 0.2, -3.0]))   # through z = 0 in the second step
+        mk = lambda: DroneBatch(p, n, device=DEV, auto_reset=True, track_episodes=True)   # noqa: E731
+        acts = torch.from_numpy(sticks.ema_noise(2 * k, range(n), seed=3)).to(DEV)
+    else:
+        pid = np.array([[0.004, 0.02, 1e-6], [0.003, 0.01, 2e-6], [0.002, 0.005, 0]])
+        p = params_1k.replace(mode=1, racer_pid=pid, racer_omega_dt=(row == "racer"), ceiling=2e-5)
+        if row == "racer_cpid":
+            p = p.replace(racer_pid=-pid, racer_pid_variant=1, pid_integral_clip=0.05, pid_min_output=-0.004, pid_max_output=0.006,
+                          pid_derivative_transition_rate=0.3)
+        mk = lambda: RacerBatch(p, n, device=DEV, auto_reset=True, track_episodes=True)   # noqa: E731
+        acts = torch.from_numpy(np.concatenate([rng.uniform(-6, 6, (2 * k, n, 3)), rng.uniform(0, 8, (2 * k, n, 1))], axis=2).astype(np.float32)).to(DEV)
+    one, many = mk(), mk()
+    one.reset(); many.reset()
+    dones = 0
+    for t in range(2 * k):
+        one.step(acts[t]) if row != "ground" else one.step(acts[t], return_imu=False)
+        dones += int(one.done.sum())
+    for c in range(2):
+        many.rollout(acts[c * k:(c + 1) * k], **dict(rollout=dict(fused=False), step_n={}, graph=dict(graph=True))[how])
+    torch.cuda.synchronize()
+    assert one.step_counter() == many.step_counter() == 2 * k
+    for name in ("state", "reward", "done_u8", "ep_return", "ep_length", "last_return", "last_length"):
+        assert torch.equal(getattr(one, name), getattr(many, name)), (row, how, name)
+    assert row == "ground" or dones > 0, "the ceiling must end some episodes"

@@ -360,3 +360,33 @@ def test_refused_combinations_raise_with_their_message():
     _lib.check(L.fpv_set_physics(b._handle, None, 0))                       # unbound: the plain kernels again
     assert b.algorithmic_bytes() == 133
     b.step(sticks, return_imu=False)
+
+
+@pytest.mark.parametrize("how", ["rollout", "step_n", "graph"])
+@pytest.mark.parametrize("row", ["plain", "objects", "noise", "reset_pose"])
+def test_table_rows_on_the_multi_step_calls_equal_single_steps(row, how):
+    """A table alone, with an object list, with stick noise and with a reset-pose table under a tight ceiling: fpv_rollout,
+    fpv_step_n and fpv_rollout_graph (with stick noise or a reset source handed on to fpv_step_n) leave the bits of the same
+    handle type stepped with fpv_step - 1000 drones, two calls of k = 5."""
+    n, k = 1000, 5
+    base = load_params(fps=1000, ceiling=10.05) if row == "reset_pose" else load_params(fps=1000)
+    kw = dict(plain={}, objects={}, noise=dict(stick_noise=True, noise_seed=9), reset_pose=dict(auto_reset=True, per_drone_reset_pose=True))[row]
+    objects = G10_OBJECTS if row == "objects" else None
+    sets = parameter_sets(base)
+    pos, vel, ypr = _poses("objects", n) if row == "objects" else _starts(n)
+    a = torch.from_numpy(_acts(2 * k, n, seed=12)).to(DEV)
+    (one, _), (many, _) = (_table_batch(base, n, sets, **kw) for _ in range(2))
+    for b in (one, many):
+        b.reset(position=pos, velocity=vel, ypr=ypr)
+    resets = 0
+    for t in range(2 * k):
+        one.step(a[t], object_list=objects or (), return_imu=False)
+        resets += int(one.done.sum())
+    for c in range(2):
+        many.rollout(a[c * k:(c + 1) * k], object_list=objects, **dict(rollout=dict(fused=False), step_n={}, graph=dict(graph=True))[how])
+    assert one.step_counter() == many.step_counter() == 2 * k
+    assert one.algorithmic_bytes() == many.algorithmic_bytes() == (185 if row == "objects" else 177)
+    for name in ("state", "reward", "done", "noise_state"):
+        x, y = getattr(one, name), getattr(many, name)
+        assert (x is None and y is None) or torch.equal(x.view(torch.uint8), y.view(torch.uint8)), name
+    assert row != "reset_pose" or resets > n // 4, "the ceiling must reset lanes in these steps"

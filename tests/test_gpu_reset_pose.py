@@ -277,3 +277,26 @@ def test_guidance_override_and_racer_refuse_a_reset_source():
     from fpyv_amd.env import RacerBatch
     with pytest.raises(ValueError):
         RacerBatch(None, 256, device=DEV, per_drone_reset_pose=True)
+
+
+@pytest.mark.parametrize("row,how", [(r, h) for r in ("table", "jitter", "aos", "fp16") for h in ("rollout", "step_n", "graph")
+                                     if (r, h) != ("aos", "step_n")])          # (fpv_step_n writes no AoS head)
+def test_reset_source_rows_on_the_multi_step_calls_equal_single_steps(row, how):
+    """The reset-pose table, the jitter, the table with the AoS head and with fp16 state: fpv_rollout, fpv_step_n and
+    fpv_rollout_graph (which hands a reset source on to fpv_step_n, or to fpv_rollout when the AoS head is written) leave the
+    bits of the same handle type stepped with fpv_step - 1000 drones, two calls of k = 5, many lanes above the ceiling at once."""
+    n, k = 1000, 5
+    kw = dict(table={}, jitter=dict(jitter=True), aos=dict(with_obs_aos=True), fp16=dict(fp16_state=True, rounding_seed=7))[row]
+    one, many = _batch(n, **kw), _batch(n, **kw)
+    for b in (one, many):
+        b.state[2] += 0.15                                          # the position rows are fp32 in either layout
+    acts, resets = _actions(2 * k, n, seed=17), 0
+    for t in range(2 * k):
+        one.step(acts[t], return_imu=False)
+        resets += int(one.done.sum())
+    for c in range(2):
+        many.rollout(acts[c * k:(c + 1) * k], **dict(rollout=dict(fused=False), step_n={}, graph=dict(graph=True))[how])
+    assert resets > n // 4 and one.step_counter() == many.step_counter() == 2 * k
+    for name in ("state", "state_h", "obs_aos", "reward", "done"):
+        x, y = getattr(one, name), getattr(many, name)
+        assert (x is None and y is None) or torch.equal(x.view(torch.uint8), y.view(torch.uint8)), name
