@@ -31,6 +31,7 @@ FPV_GATE_FLOATS = 16          # a descriptor row: c3 n3 u3 w3 a hz zc r2 (fpv_ab
 GATE_SHAPES = {"rectangle": 0, "circle": 1, "half_circle": 2}
 GATE_EVENT_NONE, GATE_EVENT_PASS, GATE_EVENT_MISS, GATE_EVENT_FINISH = 0, 1, 2, 3
 GATE_OBS_ROWS = 6
+FPV_MAX_RAYS = 32             # fpv_range_scan: a ray set has 1..32 body-frame directions (fpv_abi.h "Range scan")
 FPV_HALF_PAIR_ROWS = 5
 FPV_HALF_HALVES = 11          # binary16 values per drone in state_h (5 pair rows + 1 half row)
 FPV_OBS_AOS_DIM = 16
@@ -47,7 +48,8 @@ EXPORTS = ("fpv_abi_version", "fpv_sizeof", "fpv_state_rows", "fpv_algorithmic_b
            "fpv_allgather_done", "fpv_allgather_f32", "fpv_last_error",
            "fpv_error_name", "fpv_encoding_id", "fpv_reset_pose_sample",
            "fpv_physics_rows", "fpv_physics_derive", "fpv_physics_sample", "fpv_set_physics", "fpv_get_physics",
-           "fpv_gates_derive", "fpv_set_gates", "fpv_gate_eval")
+           "fpv_gates_derive", "fpv_set_gates", "fpv_gate_eval",
+           "fpv_rays_derive", "fpv_range_scan", "fpv_range_eval")
 
 
 class FpvParams(C.Structure):
@@ -207,6 +209,26 @@ def pack_course(count: int, laps: int = 0, gate_rewards=None, miss_is_done: bool
     return c
 
 
+class FpvRangeScan(C.Structure):
+    """fpv_range_scan_t: a ray set, its reach, the rows the ranges go to (device for fpv_range_scan, host for fpv_range_eval) and
+    the object list (host memory, read during the call)."""
+    _fields_ = [("struct_size", C.c_uint32), ("ray_count", C.c_int32), ("rays", (C.c_float * 3) * FPV_MAX_RAYS), ("max_range", C.c_float),
+                ("ranges", C.c_void_p), ("ranges_ld", C.c_int64), ("objects", C.c_void_p)]
+
+
+def pack_range_scan(rays, max_range: float) -> FpvRangeScan:
+    """The constants of a scan (`ranges`, `ranges_ld` and `objects` are the caller's to fill): `rays` [R, 3] float32 as
+    fpyv_amd.rays.derive wrote them."""
+    rows = [[float(x) for x in r] for r in rays]
+    if not 1 <= len(rows) <= FPV_MAX_RAYS or any(len(r) != 3 for r in rows):
+        raise ValueError(f"a ray set is [R, 3] with 1 <= R <= {FPV_MAX_RAYS}")
+    s = FpvRangeScan()
+    s.struct_size, s.ray_count, s.max_range = C.sizeof(FpvRangeScan), len(rows), float(max_range)
+    for k, r in enumerate(rows):
+        s.rays[k][:] = r
+    return s
+
+
 class FpvCacheModel(C.Structure):
     """fpv_cache_model_t: what a device says about itself, held against the cache model of the rotation / row stride."""
     _fields_ = [("struct_size", C.c_uint32), ("matches", C.c_int32), ("compute_units", C.c_int32), ("xcds", C.c_int32),
@@ -294,10 +316,14 @@ def lib() -> C.CDLL:
     L.fpv_gates_derive.argtypes = [C.c_int, vp, vp]
     L.fpv_set_gates.argtypes = [vp, C.POINTER(FpvGateCourse)]
     L.fpv_gate_eval.argtypes = [C.POINTER(FpvGateCourse), i64, vp, vp, vp, vp, vp, C.c_int, vp, vp, vp, vp, vp, vp]
+    L.fpv_rays_derive.argtypes = [C.c_int, vp, vp]
+    L.fpv_range_scan.argtypes = [vp, pb, C.POINTER(FpvRangeScan), vp]
+    L.fpv_range_eval.argtypes = [C.POINTER(FpvRangeScan), i64, vp, vp]
     if L.fpv_abi_version() != FPV_ABI_VERSION:
         raise ImportError(f"libfpv_hip.so ABI {L.fpv_abi_version()} != binding {FPV_ABI_VERSION} - rebuild the library "
                           "(`python -c 'import __graft_entry__ as g; g.build()'`)")
-    for which, struct in ((0, FpvParams), (1, FpvBuffers), (2, FpvObjects), (3, FpvPidParams), (4, FpvCacheModel), (5, FpvGateCourse)):
+    for which, struct in ((0, FpvParams), (1, FpvBuffers), (2, FpvObjects), (3, FpvPidParams), (4, FpvCacheModel), (5, FpvGateCourse),
+                          (6, FpvRangeScan)):
         if L.fpv_sizeof(which) != C.sizeof(struct):
             raise ImportError(f"{struct.__name__}: ctypes declares {C.sizeof(struct)} bytes, libfpv_hip.so has "
                               f"{L.fpv_sizeof(which)} - _lib.py and include/fpv_abi.h are out of step")

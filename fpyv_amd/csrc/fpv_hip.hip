@@ -35,6 +35,7 @@
 #include "fpv_derive.h"
 #include "fpv_math.h"
 #include "fpv_kernels.h"
+#include "fpv_range.h"
 
 namespace {
 
@@ -837,6 +838,8 @@ extern "C" __attribute__((weak, visibility("hidden"))) void* fpv_phys_roll_kerne
 extern "C" __attribute__((weak, visibility("hidden"))) void* fpv_gate_step_kernel(void);
 extern "C" __attribute__((weak, visibility("hidden"))) void* fpv_gate_roll_kernel(int noise, int obj);
 extern "C" __attribute__((weak, visibility("hidden"))) void* fpv_gate_reset_kernel_fn(void);
+// The kernel of csrc/fpv_range.hip, weak in the same way (fpv_range_scan says so when it is absent): one FpvRangeArgs.
+extern "C" __attribute__((weak, visibility("hidden"))) void* fpv_range_scan_kernel_fn(void);
 
 namespace {
 
@@ -1350,7 +1353,8 @@ int fpv_sizeof(int which)
         case 3: return (int)sizeof(fpv_pid_params_t);
         case 4: return (int)sizeof(fpv_cache_model_t);
         case 5: return (int)sizeof(fpv_gate_course_t);
-        default: return fail(FPV_EINVAL, "fpv_sizeof: 0 = fpv_params_t, 1 = fpv_buffers_t, 2 = fpv_objects_t, 3 = fpv_pid_params_t, 4 = fpv_cache_model_t, 5 = fpv_gate_course_t");
+        case 6: return (int)sizeof(fpv_range_scan_t);
+        default: return fail(FPV_EINVAL, "fpv_sizeof: 0 = fpv_params_t, 1 = fpv_buffers_t, 2 = fpv_objects_t, 3 = fpv_pid_params_t, 4 = fpv_cache_model_t, 5 = fpv_gate_course_t, 6 = fpv_range_scan_t");
     }
 }
 
@@ -1529,6 +1533,95 @@ int fpv_gate_eval(const fpv_gate_course_t* c, int64_t n, const float* p_old, con
             FpvQuat q; q.w = qa[0]; q.x = qa[1]; q.y = qa[2]; q.z = qa[3];
             fpv_gate_obs(fpv_gate_cn(tab + fpv_gate_index(w, G.count) * FPV_GATE_GROUPS), q, pa[0], pa[1], pa[2], obs + 6 * i);
         }
+    }
+    return FPV_OK;
+}
+
+int fpv_rays_derive(int count, const double* dirs, float* out)
+{
+    if (!dirs || !out) return fail(FPV_EINVAL, "null argument");
+    if (count < 1 || count > FPV_MAX_RAYS) return fail(FPV_EPARAM, "a ray set has 1.." + std::to_string(FPV_MAX_RAYS) + " rays, not " + std::to_string(count));
+    int bad = -1;
+    const char* why = "";
+    const int rc = fpv_derive_rays(count, dirs, out, &bad, &why);
+    return rc == FPV_OK ? FPV_OK : fail(rc, "ray " + std::to_string(bad) + ": " + why);
+}
+
+namespace {
+
+// the uniform constants of a scan and its object list, checked (everything of fpv_range_scan_t but `ranges`): FPV_OK or the error
+int range_constants(const fpv_range_scan_t* s, FpvRangeK* K, FpvObjects* T)
+{
+    if (s->struct_size != sizeof(fpv_range_scan_t)) return fail(FPV_EINVAL, "fpv_range_scan_t.struct_size does not match this library");
+    if (s->ray_count < 1 || s->ray_count > FPV_MAX_RAYS)
+        return fail(FPV_EINVAL, "ray_count: a ray set has 1.." + std::to_string(FPV_MAX_RAYS) + " rays, not " + std::to_string(s->ray_count));
+    if (!isfinite(s->max_range) || !(s->max_range > 0.0f)) return fail(FPV_EINVAL, "max_range must be finite and positive");
+    memset(K, 0, sizeof(*K));
+    memset(T, 0, sizeof(*T));
+    K->max_range = s->max_range; K->ray_count = s->ray_count;
+    for (int r = 0; r < s->ray_count; ++r) {
+        const float* d = s->rays[r];
+        const double l2 = (double)d[0] * d[0] + (double)d[1] * d[1] + (double)d[2] * d[2];
+        if (!(fabs(l2 - 1.0) <= 1.0e-4)) return fail(FPV_EINVAL, "ray " + std::to_string(r) + " is not a unit direction (rays come from fpv_rays_derive)");
+        for (int j = 0; j < 3; ++j) K->rays[r][j] = d[j];
+    }
+    if (s->objects && s->objects->count != 0) {
+        if (s->objects->count < 0 || s->objects->count > FPV_MAX_OBJECTS)
+            return fail(FPV_EINVAL, "objects.count out of range (at most " + std::to_string(FPV_MAX_OBJECTS) + " objects)");
+        T->count = s->objects->count;
+        for (int k = 0; k < T->count; ++k) {
+            const fpv_object_t& o = s->objects->obj[k];
+            if (o.type < FPV_OBJ_GROUND || o.type > FPV_OBJ_SPHERE) return fail(FPV_EINVAL, "unknown object type");
+            T->o[k].type = o.type; T->o[k].x = o.x; T->o[k].y = o.y; T->o[k].z = o.z; T->o[k].radius = o.radius; T->o[k].height = o.height;
+        }
+    }
+    fpv_range_bounds(*T, K->max_range, K->near);
+    return FPV_OK;
+}
+
+}  // namespace
+
+int fpv_range_scan(fpv_handle_t h, const fpv_buffers_t* b, const fpv_range_scan_t* s, void* stream)
+{
+    if (!fpv_range_scan_kernel_fn)        // (asked first: what a build without the kernel answers to any scan)
+        return fail(FPV_EINVAL, "the range scan is not in this build (the library was linked without csrc/fpv_range.hip)");
+    if (!h) return fail(FPV_EINVAL, "null handle");
+    if (!b || !s) return fail(FPV_EINVAL, "null argument");
+    if (h->K.flags & FPV_FLAG_FP16_STATE)
+        return fail(FPV_EINVAL, "the range scan cannot read fp16 state (FPV_FLAG_FP16_STATE): a reader of the packed quaternion is the follow-up");
+    if (!b->state) return fail(FPV_EINVAL, "fpv_buffers_t.state is null");
+    if (b->ld < h->n) return fail(FPV_EALIGN, "fpv_buffers_t.ld is smaller than the number of drones");
+    FpvRangeArgs A;
+    memset(&A, 0, sizeof(A));
+    const int rc = range_constants(s, &A.K, &A.T);
+    if (rc != FPV_OK) return rc;
+    if (!s->ranges) return fail(FPV_EINVAL, "fpv_range_scan_t.ranges is null");
+    if ((uintptr_t)s->ranges & 3) return fail(FPV_EALIGN, "ranges must be 4-byte aligned");
+    if (s->ranges_ld < h->n) return fail(FPV_EALIGN, "ranges_ld is smaller than the number of drones");
+    if (s->ranges_ld % 4) return fail(FPV_EALIGN, "ranges_ld must be a multiple of 4 floats");
+    A.state = b->state; A.ld = b->ld; A.ranges = s->ranges; A.ranges_ld = s->ranges_ld; A.n = h->n;
+    const DeviceGuard dev(h->device);
+    if (dev.rc != FPV_OK) return dev.rc;
+    void* arg = &A;
+    return launch_args("range scan launch", fpv_range_scan_kernel_fn(), blocks_for(h->n, kStepBlock), dim3(kStepBlock), (hipStream_t)stream, &arg);
+}
+
+int fpv_range_eval(const fpv_range_scan_t* s, int64_t n, const float* p, const float* q)
+{
+    if (!s || !p || !q) return fail(FPV_EINVAL, "null argument");
+    if (n <= 0) return fail(FPV_EINVAL, "n must be positive");
+    FpvRangeK K;
+    FpvObjects T;
+    const int rc = range_constants(s, &K, &T);
+    if (rc != FPV_OK) return rc;
+    if (!s->ranges) return fail(FPV_EINVAL, "fpv_range_scan_t.ranges is null");
+    if (s->ranges_ld < n) return fail(FPV_EALIGN, "ranges_ld is smaller than n");
+    if (s->ranges_ld % 4) return fail(FPV_EALIGN, "ranges_ld must be a multiple of 4 floats");
+    float* const out = s->ranges;
+    const int64_t ld = s->ranges_ld;
+    for (int64_t i = 0; i < n; ++i) {
+        FpvQuat a; a.w = q[4 * i]; a.x = q[4 * i + 1]; a.y = q[4 * i + 2]; a.z = q[4 * i + 3];
+        fpv_range_lane(K, T, a, p[3 * i], p[3 * i + 1], p[3 * i + 2], [&](int r, float t) { out[(int64_t)r * ld + i] = t; });
     }
     return FPV_OK;
 }

@@ -199,6 +199,13 @@ class _Handle:
         with torch.cuda.stream(stream):                  # None: the current stream
             return action.to(torch.float32).contiguous()
 
+    def _range_scan_raw(self, scan: "_lib.FpvRangeScan", stream: Optional[torch.cuda.Stream] = None) -> None:
+        """One fpv_range_scan of this handle's drones on `stream` (None: torch's current stream): the state, the step counter and
+        the rotation of the traversal are left alone."""
+        rc = self._L.fpv_range_scan(self._handle, self._buf_ref, C.byref(scan), self._stream() if stream is None else stream.cuda_stream)
+        if rc < 0:
+            _lib.check(rc)
+
     def _widen(self, cols: int) -> torch.Tensor:
         """fp16 storage decoded into a fresh float32 [14, cols] tensor: one launch of fpv_widen_state on torch's current stream,
         a copy valid for as long as the caller keeps it."""
@@ -216,7 +223,8 @@ class _Batch(_Handle):
                  stick_noise: bool = False, noise_seed: int = 0, drone_id_offset: int = 0,
                  with_action_out: bool = False, kahan_position: bool = False, per_drone_reset_pose: bool = False,
                  per_drone_physics: bool = False, gates: Any = None, laps: int = 0, gate_rewards: Optional[Dict[str, float]] = None,
-                 miss_is_done: bool = False, gate_obs: bool = True, gate_start: Any = None):
+                 miss_is_done: bool = False, gate_obs: bool = True, gate_start: Any = None, range_rays: Any = None,
+                 range_max: float = 20.0):
         if num_envs <= 0:
             raise ValueError("num_envs must be positive")
         device = torch.device(device)
@@ -283,6 +291,16 @@ class _Batch(_Handle):
             # (the library refuses the table on a Racer or fp16-state handle here, and with Kahan rows, the guidance override or
             # the AoS head at the launch that combines them - each by name)
             _lib.check(self._L.fpv_set_physics(self._handle, self.physics.data_ptr(), self.ld))
+        # the range sensor (fpv_range_scan): `range_rays` [R, 3] unit body-frame directions (fpyv_amd.rays.derive of what was given),
+        # `range_rows` [R, ld] the rows a scan writes - an output: checkpoints do not carry them
+        self.range_rays = self.range_rows = self._scan = None
+        self._scan_objects = self._scan_object_rows = None
+        if range_rays is not None:
+            from . import rays as _rays
+            self.range_rays = _rays.derive(range_rays)
+            self.range_rows = torch.zeros((self.range_rays.shape[0], self.ld), **f32)
+            self._scan = _lib.pack_range_scan(self.range_rays, range_max)
+            self._scan.ranges, self._scan.ranges_ld = self.range_rows.data_ptr(), self.ld
         self._objects = None            # the bound fpv_objects_t (None = no collision world bound)
         self._object_rows = None
         self._override_keep = None
@@ -616,6 +634,37 @@ class _Batch(_Handle):
             self._objects = None
             self._buf.objects = None
 
+    # -- range sensor ------------------------------------------------------------------------------
+    def _scan_world(self, object_list) -> None:
+        """The object list of the next scan: given, it is converted as `step` converts it into the scan's own table (nothing is
+        bound to the steps: a Racer can see a world it does not collide with); None takes what `set_objects` or the last `step`
+        bound, the empty list if nothing is."""
+        if self._scan is None:
+            raise ValueError("this batch was built without range_rays=")
+        if object_list is None:
+            self._scan.objects = self._buf.objects
+            return
+        from .objects import to_rows
+        rows = to_rows(object_list)
+        if rows != self._scan_object_rows or self._scan_objects is None:      # a world that did not move is not re-packed
+            self._scan_objects = _lib.pack_objects(rows)
+            self._scan_object_rows = rows
+        self._scan.objects = C.addressof(self._scan_objects)
+
+    def range_scan(self, object_list=None) -> torch.Tensor:
+        """One scan of the range sensor on torch's current stream: for every ray of `range_rays` and every drone, the distance
+        along the ray (body frame, turned by the drone's attitude) to the nearest Ground / Cylinder / Target of `object_list`,
+        at most `range_max`; 0 from inside an object.  Returns `ranges`.  The scan reads the position and the attitude only:
+        state, rewards, the step counter and the rotation of the traversal are what they were (include/fpv_abi.h "Range scan")."""
+        self._scan_world(object_list)
+        self._range_scan_raw(self._scan)
+        return self.ranges
+
+    @property
+    def ranges(self) -> Optional[torch.Tensor]:
+        """[R, num_envs] view of the range rows as the last scan wrote them (`.T`: the [num_envs, R] block of an observation)"""
+        return None if self.range_rows is None else self.range_rows[:, :self.n]
+
     def set_done_bits_target(self, target: Any = None, stride_words: int = 0) -> None:
         """Where the kernel writes the bit-packed done mask (one wave ballot per 64 drones):
         an int64 tensor of at least ceil(num_envs / 64) words or a raw device address; None restores the
@@ -787,6 +836,10 @@ class _Partition(_Handle):
         elif getattr(self, "_course", None) is not None:
             _lib.check(self._L.fpv_set_gates(self._handle, None))
             self._course = None
+        self._scan = None
+        if self.parent._scan is not None:              # the parent's ray set on this partition's columns of the range rows
+            self._scan = _lib.FpvRangeScan.from_buffer_copy(self.parent._scan)
+            self._scan.ranges = self.parent._scan.ranges + 4 * lo
 
 
 def partition_bounds(n: int, parts: int) -> Sequence[Tuple[int, int]]:
@@ -1058,7 +1111,10 @@ class FpvVecEnv:
                  wind: Sequence[float] = (0.0, 0.0, 0.0), object_list=(), partitions: int = 1, **batch_options: Any):
         """`batch_options` go to DroneBatch / RacerBatch (stick_noise=, noise_seed=, drone_id_offset=,
         fp16_state=, with_obs_aos=, kahan_position=, with_done_bits=, per_drone_physics=, ...); `object_list` is the
-        collision world of every step (fpyv_amd.objects); `partitions` > 1 enables step_async / step_wait."""
+        collision world of every step (fpyv_amd.objects); `partitions` > 1 enables step_async / step_wait.  `range_rays=`
+        (with `range_max=`) adds the range sensor: every step - and reset() - is followed by a scan of `object_list` on the same
+        stream, `ranges` [R, num_envs] and info["ranges"] hold the result (a lane that auto-reset reports its reset pose's
+        ranges, like `obs`)."""
         if mode not in ("drone", "racer"):
             raise ValueError(f'mode must be "drone" or "racer", got {mode!r}')
         params = params if params is not None else load_params(fps=1000)
@@ -1132,12 +1188,14 @@ class FpvVecEnv:
             kw = dict(position=position, velocity=velocity, ypr=ypr)
         if not self._parts:
             self.batch.reset(mask=mask, **kw)
+            self._range_scan(self.batch)
             return self.obs
         cur = self._caller_waits_for_partitions()      # steps still in flight on the partitions' streams finish first
         if self.batch._cparams.flags & _lib.FPV_FLAG_RESET_JITTER:
             # the jitter of an explicit reset is keyed by the step counter: the partitions', which stepped this population
             self.batch.set_step_counter(min(P._steps_launched for P in self._parts))
         self.batch.reset(mask=mask, **kw)              # (the step counters run on, as the unpartitioned batch's does across a reset)
+        self._range_scan(self.batch)
         self._partitions_wait_for(cur)
         return self.obs
 
@@ -1160,6 +1218,22 @@ class FpvVecEnv:
         """[num_envs, 6] view of the gate observation rows (DroneBatch.gate_obs)"""
         return self.batch.gate_obs
 
+    @property
+    def ranges(self) -> Optional[torch.Tensor]:
+        """[R, num_envs] view of the range rows after the last step or reset (None without range_rays=); `.T` is the
+        [num_envs, R] block a policy concatenates to `obs`"""
+        return self.batch.ranges
+
+    def _range_scan(self, stepper: _Handle, stream: Optional[torch.cuda.Stream] = None) -> None:
+        """The range sensor after a step or a reset of `stepper` (the batch, or a partition on its own stream): the env's
+        collision world, the columns of `stepper`."""
+        b = self.batch
+        if b.range_rows is None:
+            return
+        b._scan_world(self.object_list)
+        stepper._scan.objects = b._scan.objects
+        stepper._range_scan_raw(stepper._scan, stream)
+
     def _whole_population(self, fn, *a, **kw) -> None:
         if not self._parts:
             fn(*a, **kw)
@@ -1180,6 +1254,7 @@ class FpvVecEnv:
             return self.obs, self.batch.reward, self.batch.done, self._info(self.batch, 0, self.num_envs)
         self._bind_world(self.batch)
         self.batch._step_raw(action)
+        self._range_scan(self.batch)
         return self.obs, self.batch.reward, self.batch.done, self._info(self.batch, 0, self.num_envs)
 
     def _bind_world(self, stepper: _Handle) -> None:
@@ -1201,6 +1276,8 @@ class FpvVecEnv:
         if getattr(batch, "gate_word", None) is not None:              # a gate course: the race state after this step
             w = batch.gate_word[lo:hi]
             info["gates_passed"], info["gate_event"] = (w >> 10) & 0x3FFFFF, (w >> 8) & 3
+        if getattr(batch, "range_rows", None) is not None:             # the range sensor: [R, columns] after this step's scan
+            info["ranges"] = batch.range_rows[:, lo:hi]
         return info
 
     # -- split phase ------------------------------------------------------------------------------
@@ -1236,6 +1313,7 @@ class FpvVecEnv:
                 P.stream.wait_stream(cur)
         self._bind_world(P)
         P._step_raw(action, stream=P.stream)
+        self._range_scan(P, P.stream)
 
     def step_wait(self, part: int, sync: bool = True) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor, Dict[str, Any]]:
         """(obs, reward, done, info) of partition `part` - views of its columns - ordered after its last enqueued step:

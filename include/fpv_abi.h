@@ -537,6 +537,43 @@ int fpv_gate_eval(const fpv_gate_course_t* course, int64_t n, const float* p_old
                   const uint8_t* physics_done, const uint32_t* word_in, int auto_reset, const float* p_after, const float* q_after,
                   uint32_t* word_out, float* reward, uint8_t* done, float* obs);
 
+/* ---- Range scan: body-frame ray distances to the object list (build-defined; the reference's Camera over point clouds is out
+ * of scope) ----------------------------------------------------------------------------------------------------------------
+ * A ray set is 1..FPV_MAX_RAYS unit directions d_b in the body frame.  The ray r of drone i starts at its position p_i and runs
+ * along d = R(q_i) d_b (body -> world, not renormalised); a range is the parameter t along d.  Every object of the list is a
+ * convex solid in the geometry the collisions use - Ground the half-space z <= 0, Cylinder (x-ob.x)^2 + (y-ob.y)^2 <= radius^2
+ * with ob.z <= z <= ob.z + height, Target (sphere) the ball of `radius` - met by a ray in one interval [t_in, t_out]; it is hit
+ * when t_in <= t_out and t_out >= 0, at range max(t_in, 0) (0 from inside).  ranges[r][i] = min(max_range, nearest hit); a ray
+ * that hits nothing, an empty or NULL list: max_range.  Rays parallel to a constraint (|d_z| < 1e-12 for the ground and a
+ * cylinder's caps, d_x^2 + d_y^2 < 1e-24 for its wall) satisfy it always or never; no input gives a NaN.  Gates and trails are
+ * not seen.  ONE definition (csrc/fpv_range.h fpv_range_lane) is run by the kernel (csrc/fpv_range.hip) and by fpv_range_eval on
+ * the host: the same bits.  The scan is a kernel of its own: it serves every fp32 handle (drone or Racer; a physics table, a gate
+ * course, stick noise, reset sources, partitions), leaves the state, the step counter and the rotation of the traversal alone,
+ * and moves 28 + 4 ray_count bytes per drone. */
+#define FPV_MAX_RAYS 32
+typedef struct fpv_range_scan {
+    uint32_t struct_size;               /* sizeof(fpv_range_scan_t) = fpv_sizeof(6) */
+    int32_t  ray_count;                 /* 1..FPV_MAX_RAYS */
+    float    rays[FPV_MAX_RAYS][3];     /* body-frame directions as fpv_rays_derive wrote them (unit to 1e-4) */
+    float    max_range;                 /* finite, > 0 */
+    float*   ranges;                    /* [ray_count][ranges_ld] fp32, write-only; DEVICE for fpv_range_scan, HOST for fpv_range_eval */
+    int64_t  ranges_ld;                 /* >= n, multiple of 4 */
+    const fpv_objects_t* objects;       /* host memory, read during the call (as fpv_buffers_t.objects); NULL or count 0: nothing to hit */
+} fpv_range_scan_t;
+
+/* out[k] = dirs[k] / |dirs[k]|, normalised in double and narrowed once (host arithmetic only).  FPV_EPARAM, naming the ray
+ * ("ray <index>: ..."), for a zero or non-finite direction or a count outside 1..FPV_MAX_RAYS. */
+int fpv_rays_derive(int count, const double* dirs /*[count][3]*/, float* out /*[count][3]*/);
+/* One scan of the handle's n drones at b->state / b->ld on `stream`, under the handle's device: allocates nothing, never
+ * synchronises, does not advance the step index and does not touch the rotation.  FPV_EINVAL / FPV_EALIGN, by name: fp16 state
+ * (the packed quaternion has no reader here - the named follow-up), a wrong struct_size, ray_count out of range, rays that are
+ * not unit, max_range not finite or not positive, null ranges, ranges_ld < n or not a multiple of 4, more than FPV_MAX_OBJECTS
+ * objects or an unknown object type; and in a library built without csrc/fpv_range.hip. */
+int fpv_range_scan(fpv_handle_t h, const fpv_buffers_t* b, const fpv_range_scan_t* s, void* stream);
+/* The kernel's own lane function on the host (no handle, no device): drone i of n at p[i][3] with attitude q[i][4] (wxyz);
+ * s->ranges is HOST memory. */
+int fpv_range_eval(const fpv_range_scan_t* s, int64_t n, const float* p /*[n][3]*/, const float* q /*[n][4] wxyz*/);
+
 /* Row stride (in floats) to allocate for n drones.  Up to 2^18 drones: n rounded up to 64, padded so that the stride in
  * bytes is at least 1 KiB past a multiple of 8 KiB (strides at or near a multiple of 8 KiB put all 14
  * rows on the same HBM channel/bank set).  Beyond: the smallest ld >= n that is 256 mod 512 floats (1 KiB past a multiple of
