@@ -96,11 +96,17 @@ FPV_HD float fpv_clamp(float x, float lo, float hi)
 #endif
 }
 
-// Correctly rounded sqrt of x >= 0 with everything below the smallest normal float flushed to 0 (the arguments are
-// sums of squares of speeds / distances: 1e-19 m/s is nothing).  The host build calls sqrtf; the kernel issues
-// v_sqrt_f32 (1 ulp) and the compiler's own two-sided correction step, but not the x 2^32 pre-scaling, the un-scaling
-// and the zero / infinity class test that `sqrtf` carries for denormal arguments: 11 instructions instead of 16,
-// the same bits for every normal x, +0 and +inf.
+// Correctly rounded sqrt of x >= 0 with everything below 2^-96 flushed to 0 (the arguments are sums of squares of speeds /
+// distances: a root below 2^-48 = 3.6e-15 m or m/s is nothing).  The host build calls sqrtf; the kernel issues v_sqrt_f32
+// (1 ulp) and the compiler's own two-sided correction step, but not the x 2^32 pre-scaling, the un-scaling and the zero /
+// infinity class test that `sqrtf` carries for every argument below 2^-96: 11 instructions instead of 16.
+// Device and host return the same bits for every x >= 2^-96, +inf included, and 0 for every x below, +0 included - the set
+// tests/test_gpu_device_math.py sweeps.  Why 2^-96 and not the smallest normal: the error terms e_dn and e_up are multiples
+// of 2^(2 e_r - 46), 2^e_r <= r < 2^(e_r + 1), and have to be EXACT for the sign tests to pick the right neighbour.  With
+// fp32 denormals kept (every kernel's descriptor asks for that, tests/test_isa_denorm_mode.py) they are for x >= 2^-103;
+// below, an e_dn that rounds to +0 replaces a correct root by r_dn.  2^-96 is the compiler's own scaling threshold and leaves
+// seven binades of margin.
+#define FPV_SQRT_FLUSH_BELOW 1.26217745e-29f   // 2^-96
 FPV_HD float fpv_sqrt_flushed(float x)
 {
 #if defined(__HIP_DEVICE_COMPILE__)
@@ -109,9 +115,9 @@ FPV_HD float fpv_sqrt_flushed(float x)
     const float e_dn = fmaf(-r_dn, r, x), e_up = fmaf(-r_up, r, x);
     float y = e_dn <= 0.0f ? r_dn : r;
     y = e_up > 0.0f ? r_up : y;
-    return x < 1.17549435e-38f ? 0.0f : y;
+    return x < FPV_SQRT_FLUSH_BELOW ? 0.0f : y;
 #else
-    return x < 1.17549435e-38f ? 0.0f : sqrtf(x);
+    return x < FPV_SQRT_FLUSH_BELOW ? 0.0f : sqrtf(x);
 #endif
 }
 
@@ -317,10 +323,10 @@ FPV_HD uint16_t fpv_f32_to_f16_rn(float x)
     if (a > 0x7f800000u) return (uint16_t)(sign | 0x7e00u);                                // nan
     if (a >= 0x477ff000u) return (uint16_t)(sign | 0x7c00u);                               // >= 65520 -> inf
     if (a < 0x38800000u) {                                                                 // below the smallest normal half
-        const float t = fpv_bits_f32(a) * 16777216.0f;                                     // value / 2^-24, exact
-        uint32_t q = (uint32_t)(t + 0.5f);
-        if ((t + 0.5f) == (float)q && (q & 1u)) q -= 1u;                                   // ties to even
-        return (uint16_t)(sign | q);
+        // value / 2^-24, exact; rintf rounds it once, ties to even (adding 0.5f first rounded 2^-25 (1 + 2^-23), whose sum
+        // 1 + 2^-24 is not a float, to the tie it is just above: 0 where v_cvt_f16_f32 and numpy.float16 give 2^-24)
+        const float t = fpv_bits_f32(a) * 16777216.0f;
+        return (uint16_t)(sign | (uint32_t)rintf(t));
     }
     a += 0xfffu + ((a >> 13) & 1u);
     return (uint16_t)(sign | ((a - 0x38000000u) >> 13));

@@ -186,9 +186,10 @@ def test_bitwise_equal_to_lane_model_ragged_sizes(params_1k, n):
 
 def test_edge_inputs_bitwise_equal_to_lane_model(params_1k):
     """The two places where the kernel does NOT execute the host's instructions - the clip (one v_med3_f32 against
-    fminf(fmaxf())) and the square root (v_sqrt_f32 + correction, arguments below the smallest normal flushed to zero,
-    against sqrtf) - on the inputs a flight never produces: NaN and infinite sticks, sticks far outside [-1, 1],
-    velocities whose square is subnormal, sits on the flush boundary, or is near the top of the fp32 range."""
+    fminf(fmaxf())) and the square root (v_sqrt_f32 + correction, arguments below 2^-96 flushed to zero, against sqrtf) -
+    on the inputs a flight never produces: NaN and infinite sticks, sticks far outside [-1, 1], velocities whose square is
+    subnormal, lies below the flush threshold, or is near the top of the fp32 range.  (The speed these roots feed multiplies
+    a drag term that is rounded away: the sweep that can see a wrong root is tests/test_gpu_device_math.py.)"""
     vels = np.array([[0, 0, 0], [1e-30, 0, 0], [1e-20, -1e-20, 1e-21], [1.05e-19, 0, 0], [1.1e-19, 0, 0], [7.7e-20, 7.7e-20, 0],
                      [1e-15, 0, 0], [3e18, -2e18, 1e18], [1e19, 0, 0], [-0.0, 0.0, -0.0]], dtype=np.float32)
     sticks_ = np.array([[np.nan, 0, 0, 0], [0, np.nan, np.nan, -0.5], [np.inf, -np.inf, 1e30, 0.2], [5, -7, 1.0000001, -1.5],

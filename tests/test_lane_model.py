@@ -218,6 +218,11 @@ def test_fp16_conversions_match_ieee_and_stochastic_rounding_is_unbiased():
     xs = rng.standard_normal(5000).astype(np.float32) * np.float32(10.0) ** rng.integers(-9, 5, 5000).astype(np.float32)
     xs = np.concatenate([xs, np.array([0, -0.0, 65504, 65519.9, 65520, 7e4, -7e4, 6e-8, 3e-8, 2.98e-8, 5.96e-8,
                                        6.1e-5, 6.09e-5, 1.0, -1.0], dtype=np.float32)])
+    # every tie between two subnormal halves, (k + 1/2) 2^-24, and its two float32 neighbours, both signs: 2^-25 (1 + 2^-23) is
+    # where adding 0.5f before truncating went wrong (the sum is not a float and rounds onto the tie)
+    ties = ((np.arange(1024) + 0.5) * 2.0 ** -24).astype(np.float32)
+    ties = np.concatenate([ties, np.nextafter(ties, np.float32(0)), np.nextafter(ties, np.float32(1))])
+    xs = np.concatenate([xs, ties, -ties])
     with np.errstate(over="ignore"):
         ref = xs.astype(np.float16)
     for x, r in zip(xs, ref):
