@@ -32,6 +32,8 @@ GATE_SHAPES = {"rectangle": 0, "circle": 1, "half_circle": 2}
 GATE_EVENT_NONE, GATE_EVENT_PASS, GATE_EVENT_MISS, GATE_EVENT_FINISH = 0, 1, 2, 3
 GATE_OBS_ROWS = 6
 FPV_MAX_RAYS = 32             # fpv_range_scan: a ray set has 1..32 body-frame directions (fpv_abi.h "Range scan")
+FPV_DEPTH_MAX_SIDE = 128      # fpv_depth_render: an image is 4..128 pixels wide and high (fpv_abi.h "Depth camera")
+DEPTH_ENCODINGS = {"metres": 0, "u8": 1}
 FPV_HALF_PAIR_ROWS = 5
 FPV_HALF_HALVES = 11          # binary16 values per drone in state_h (5 pair rows + 1 half row)
 FPV_OBS_AOS_DIM = 16
@@ -49,7 +51,8 @@ EXPORTS = ("fpv_abi_version", "fpv_sizeof", "fpv_state_rows", "fpv_algorithmic_b
            "fpv_error_name", "fpv_encoding_id", "fpv_reset_pose_sample",
            "fpv_physics_rows", "fpv_physics_derive", "fpv_physics_sample", "fpv_set_physics", "fpv_get_physics",
            "fpv_gates_derive", "fpv_set_gates", "fpv_gate_eval",
-           "fpv_rays_derive", "fpv_range_scan", "fpv_range_eval")
+           "fpv_rays_derive", "fpv_range_scan", "fpv_range_eval",
+           "fpv_camera_derive", "fpv_depth_render", "fpv_depth_eval")
 
 
 class FpvParams(C.Structure):
@@ -229,6 +232,22 @@ def pack_range_scan(rays, max_range: float) -> FpvRangeScan:
     return s
 
 
+class FpvCamera(C.Structure):
+    """fpv_camera_t: the reference's Camera arguments as fpv_camera_derive reads them."""
+    _fields_ = [("pitch_deg", C.c_double), ("relative_position", C.c_double * 3), ("fov_deg", C.c_double), ("width", C.c_int32),
+                ("height", C.c_int32)]
+
+
+class FpvDepthRender(C.Structure):
+    """fpv_depth_render_t: what fpv_camera_derive wrote, the reach and the encoding, the images (device for fpv_depth_render, host
+    for fpv_depth_eval), the object list (host memory) and the gate table (device / host like the images)."""
+    _fields_ = [("struct_size", C.c_uint32), ("width", C.c_int32), ("height", C.c_int32), ("encoding", C.c_int32),
+                ("dir0", C.c_float * 3), ("dir_u", C.c_float * 3), ("dir_v", C.c_float * 3), ("offset", C.c_float * 3),
+                ("dir_len_max", C.c_float), ("max_depth", C.c_float), ("gate_frame_width", C.c_float), ("gate_count", C.c_int32),
+                ("focal_length", C.c_double), ("relative_rotation", C.c_double * 9), ("image", C.c_void_p), ("image_stride", C.c_int64),
+                ("objects", C.c_void_p), ("gate_descriptors", C.c_void_p)]
+
+
 class FpvCacheModel(C.Structure):
     """fpv_cache_model_t: what a device says about itself, held against the cache model of the rotation / row stride."""
     _fields_ = [("struct_size", C.c_uint32), ("matches", C.c_int32), ("compute_units", C.c_int32), ("xcds", C.c_int32),
@@ -319,11 +338,14 @@ def lib() -> C.CDLL:
     L.fpv_rays_derive.argtypes = [C.c_int, vp, vp]
     L.fpv_range_scan.argtypes = [vp, pb, C.POINTER(FpvRangeScan), vp]
     L.fpv_range_eval.argtypes = [C.POINTER(FpvRangeScan), i64, vp, vp]
+    L.fpv_camera_derive.argtypes = [C.POINTER(FpvCamera), C.POINTER(FpvDepthRender)]
+    L.fpv_depth_render.argtypes = [vp, pb, C.POINTER(FpvDepthRender), vp]
+    L.fpv_depth_eval.argtypes = [C.POINTER(FpvDepthRender), i64, vp, vp]
     if L.fpv_abi_version() != FPV_ABI_VERSION:
         raise ImportError(f"libfpv_hip.so ABI {L.fpv_abi_version()} != binding {FPV_ABI_VERSION} - rebuild the library "
                           "(`python -c 'import __graft_entry__ as g; g.build()'`)")
     for which, struct in ((0, FpvParams), (1, FpvBuffers), (2, FpvObjects), (3, FpvPidParams), (4, FpvCacheModel), (5, FpvGateCourse),
-                          (6, FpvRangeScan)):
+                          (6, FpvRangeScan), (7, FpvDepthRender)):
         if L.fpv_sizeof(which) != C.sizeof(struct):
             raise ImportError(f"{struct.__name__}: ctypes declares {C.sizeof(struct)} bytes, libfpv_hip.so has "
                               f"{L.fpv_sizeof(which)} - _lib.py and include/fpv_abi.h are out of step")

@@ -9,10 +9,12 @@ the per-drone step: `from fpyv_amd.components import Drone, Ground, Cylinder, Ta
     Target  :753-778, Gate :780-831, Trail :631-644                           distance + normal only, Gate/Trail inert)
 
 `Racer` (/root/reference/tests/racer_drone_test.py:68-103) maps to fpyv_amd.env.RacerBatch.
-Camera and the guidance methods are out of scope.
+`Camera` (:449-629) maps to fpyv_amd.camera.Camera: the reference's constructor signature on the batched depth camera (DESIGN 3.8;
+its rendering of point clouds and the guidance methods are out of scope).
 """
+from .camera import Camera  # noqa: F401
 from .env import DroneBatch as Drone, RacerBatch as Racer, FpvVecEnv  # noqa: F401
 from .objects import Cylinder, Gate, Ground, Target, Trail  # noqa: F401
 from .pid import PID  # noqa: F401
 
-__all__ = ["Drone", "Racer", "FpvVecEnv", "Ground", "Cylinder", "Target", "Gate", "Trail", "PID"]
+__all__ = ["Drone", "Racer", "FpvVecEnv", "Ground", "Cylinder", "Target", "Gate", "Trail", "PID", "Camera"]

@@ -36,6 +36,7 @@
 #include "fpv_math.h"
 #include "fpv_kernels.h"
 #include "fpv_range.h"
+#include "fpv_depth.h"
 
 namespace {
 
@@ -840,6 +841,9 @@ extern "C" __attribute__((weak, visibility("hidden"))) void* fpv_gate_roll_kerne
 extern "C" __attribute__((weak, visibility("hidden"))) void* fpv_gate_reset_kernel_fn(void);
 // The kernel of csrc/fpv_range.hip, weak in the same way (fpv_range_scan says so when it is absent): one FpvRangeArgs.
 extern "C" __attribute__((weak, visibility("hidden"))) void* fpv_range_scan_kernel_fn(void);
+// The kernels of csrc/fpv_depth.hip (one per encoding), weak in the same way (fpv_depth_render says so when they are absent): one
+// FpvDepthArgs.
+extern "C" __attribute__((weak, visibility("hidden"))) void* fpv_depth_render_kernel_fn(int u8);
 
 namespace {
 
@@ -1354,7 +1358,8 @@ int fpv_sizeof(int which)
         case 4: return (int)sizeof(fpv_cache_model_t);
         case 5: return (int)sizeof(fpv_gate_course_t);
         case 6: return (int)sizeof(fpv_range_scan_t);
-        default: return fail(FPV_EINVAL, "fpv_sizeof: 0 = fpv_params_t, 1 = fpv_buffers_t, 2 = fpv_objects_t, 3 = fpv_pid_params_t, 4 = fpv_cache_model_t, 5 = fpv_gate_course_t, 6 = fpv_range_scan_t");
+        case 7: return (int)sizeof(fpv_depth_render_t);
+        default: return fail(FPV_EINVAL, "fpv_sizeof: 0 = fpv_params_t, 1 = fpv_buffers_t, 2 = fpv_objects_t, 3 = fpv_pid_params_t, 4 = fpv_cache_model_t, 5 = fpv_gate_course_t, 6 = fpv_range_scan_t, 7 = fpv_depth_render_t");
     }
 }
 
@@ -1622,6 +1627,138 @@ int fpv_range_eval(const fpv_range_scan_t* s, int64_t n, const float* p, const f
     for (int64_t i = 0; i < n; ++i) {
         FpvQuat a; a.w = q[4 * i]; a.x = q[4 * i + 1]; a.y = q[4 * i + 2]; a.z = q[4 * i + 3];
         fpv_range_lane(K, T, a, p[3 * i], p[3 * i + 1], p[3 * i + 2], [&](int r, float t) { out[(int64_t)r * ld + i] = t; });
+    }
+    return FPV_OK;
+}
+
+int fpv_camera_derive(const fpv_camera_t* camera, fpv_depth_render_t* out)
+{
+    if (!camera || !out) return fail(FPV_EINVAL, "null argument");
+    const char* why = "";
+    const int rc = fpv_depth_derive(*camera, out, &why);
+    return rc == FPV_OK ? FPV_OK : fail(rc, std::string("camera: ") + why);
+}
+
+namespace {
+
+// the uniform constants of a render and its object list, checked (everything of fpv_depth_render_t but `image` and the gate
+// table's address space): FPV_OK or the error
+int depth_constants(const fpv_depth_render_t* s, FpvDepthK* K, FpvObjects* T)
+{
+    if (s->struct_size != sizeof(fpv_depth_render_t)) return fail(FPV_EINVAL, "fpv_depth_render_t.struct_size does not match this library");
+    if (s->width < 4 || s->width > FPV_DEPTH_MAX_SIDE || s->height < 4 || s->height > FPV_DEPTH_MAX_SIDE)
+        return fail(FPV_EINVAL, "width and height must be 4.." + std::to_string(FPV_DEPTH_MAX_SIDE) + " pixels, not " + std::to_string(s->width) + " x " + std::to_string(s->height));
+    if (s->width % 4) return fail(FPV_EINVAL, "width must be a multiple of 4 (four pixels share a dword of the byte image)");
+    if (s->encoding != FPV_DEPTH_METRES && s->encoding != FPV_DEPTH_U8) return fail(FPV_EINVAL, "unknown encoding (0 FPV_DEPTH_METRES, 1 FPV_DEPTH_U8)");
+    if (!isfinite(s->max_depth) || !(s->max_depth > 0.0f)) return fail(FPV_EINVAL, "max_depth must be finite and positive");
+    if (s->gate_count < 0 || s->gate_count > FPV_MAX_GATES)
+        return fail(FPV_EINVAL, "gate_count must be 0.." + std::to_string(FPV_MAX_GATES) + ", not " + std::to_string(s->gate_count));
+    if (s->gate_count > 0) {
+        if (!s->gate_descriptors) return fail(FPV_EINVAL, "gates without descriptors (gate_descriptors is null)");
+        if ((uintptr_t)s->gate_descriptors & 15) return fail(FPV_EALIGN, "gate_descriptors must be 16-byte aligned");
+        if (!isfinite(s->gate_frame_width) || !(s->gate_frame_width > 0.0f)) return fail(FPV_EINVAL, "gate_frame_width must be finite and positive");
+    }
+    if (!isfinite(s->dir_len_max) || !(s->dir_len_max >= 1.0f)) return fail(FPV_EINVAL, "dir_len_max is not what fpv_camera_derive writes");
+    memset(K, 0, sizeof(*K));
+    memset(T, 0, sizeof(*T));
+    for (int k = 0; k < 3; ++k) {
+        if (!isfinite(s->dir0[k]) || !isfinite(s->dir_u[k]) || !isfinite(s->dir_v[k]) || !isfinite(s->offset[k]))
+            return fail(FPV_EINVAL, "direction vectors and offset must be finite (they come from fpv_camera_derive)");
+        K->a0[k] = s->dir0[k]; K->au[k] = s->dir_u[k]; K->av[k] = s->dir_v[k]; K->rel[k] = s->offset[k];
+    }
+    {   // no pixel's direction may be longer than dir_len_max says: the cull's margin rests on it
+        double worst = 0.0;
+        for (int c = 0; c < 4; ++c) {
+            const double i = (c & 1) ? s->width - 1 : 0, j = (c & 2) ? s->height - 1 : 0;
+            double l2 = 0.0;
+            for (int k = 0; k < 3; ++k) { const double d = (double)s->dir0[k] + i * s->dir_u[k] + j * s->dir_v[k]; l2 += d * d; }
+            worst = l2 > worst ? l2 : worst;
+        }
+        if (!(sqrt(worst) <= (double)s->dir_len_max * (1.0 + 1.0e-5))) return fail(FPV_EINVAL, "a pixel's direction is longer than dir_len_max (both come from fpv_camera_derive)");
+    }
+    K->max_depth = s->max_depth;
+    K->reach = fpv_depth_reach(s->max_depth, s->dir_len_max);
+    K->frame_width = s->gate_count > 0 ? s->gate_frame_width : 0.0f;
+    K->width = s->width; K->height = s->height; K->gate_count = s->gate_count;
+    if (s->objects && s->objects->count != 0) {
+        if (s->objects->count < 0 || s->objects->count > FPV_MAX_OBJECTS)
+            return fail(FPV_EINVAL, "objects.count out of range (at most " + std::to_string(FPV_MAX_OBJECTS) + " objects)");
+        T->count = s->objects->count;
+        for (int k = 0; k < T->count; ++k) {
+            const fpv_object_t& o = s->objects->obj[k];
+            if (o.type < FPV_OBJ_GROUND || o.type > FPV_OBJ_SPHERE) return fail(FPV_EINVAL, "unknown object type");
+            T->o[k].type = o.type; T->o[k].x = o.x; T->o[k].y = o.y; T->o[k].z = o.z; T->o[k].radius = o.radius; T->o[k].height = o.height;
+        }
+    }
+    fpv_range_bounds(*T, K->reach, K->near);
+    return FPV_OK;
+}
+
+int depth_image_checks(const fpv_depth_render_t* s)
+{
+    if (!s->image) return fail(FPV_EINVAL, "fpv_depth_render_t.image is null");
+    if ((uintptr_t)s->image & 3) return fail(FPV_EALIGN, "image must be 4-byte aligned");
+    if (s->image_stride < (int64_t)s->width * s->height) return fail(FPV_EALIGN, "image_stride is smaller than width * height");
+    if (s->image_stride % 4) return fail(FPV_EALIGN, "image_stride must be a multiple of 4 elements");
+    return FPV_OK;
+}
+
+}  // namespace
+
+int fpv_depth_render(fpv_handle_t h, const fpv_buffers_t* b, const fpv_depth_render_t* s, void* stream)
+{
+    if (!fpv_depth_render_kernel_fn)      // (asked first: what a build without the kernel answers to any render)
+        return fail(FPV_EINVAL, "the depth camera is not in this build (the library was linked without csrc/fpv_depth.hip)");
+    if (!h) return fail(FPV_EINVAL, "null handle");
+    if (!b || !s) return fail(FPV_EINVAL, "null argument");
+    if (h->K.flags & FPV_FLAG_FP16_STATE)
+        return fail(FPV_EINVAL, "the depth camera cannot read fp16 state (FPV_FLAG_FP16_STATE): a reader of the packed quaternion is the follow-up");
+    if (!b->state) return fail(FPV_EINVAL, "fpv_buffers_t.state is null");
+    if (b->ld < h->n) return fail(FPV_EALIGN, "fpv_buffers_t.ld is smaller than the number of drones");
+    FpvDepthArgs A;
+    memset(&A, 0, sizeof(A));
+    int rc = depth_constants(s, &A.K, &A.T);
+    if (rc != FPV_OK) return rc;
+    rc = depth_image_checks(s);
+    if (rc != FPV_OK) return rc;
+    const int64_t wpi = ((int64_t)s->width * s->height + 63) / 64, waves = wpi * h->n;
+    if (waves > ((int64_t)1 << 31)) return fail(FPV_EINVAL, "more than 2^31 waves (drones x ceil(width * height / 64)): render the population in parts");
+    A.state = b->state; A.ld = b->ld; A.gates = reinterpret_cast<const fpv_gate_v4*>(s->gate_descriptors);
+    A.image = s->image; A.image_stride = s->image_stride; A.n = h->n; A.waves_per_image = (uint32_t)wpi;
+    const DeviceGuard dev(h->device);
+    if (dev.rc != FPV_OK) return dev.rc;
+    void* arg = &A;
+    return launch_args("depth render launch", fpv_depth_render_kernel_fn(s->encoding == FPV_DEPTH_U8), blocks_for(waves, 4), dim3(256), (hipStream_t)stream, &arg);
+}
+
+int fpv_depth_eval(const fpv_depth_render_t* s, int64_t n, const float* p, const float* q)
+{
+    if (!s || !p || !q) return fail(FPV_EINVAL, "null argument");
+    if (n <= 0) return fail(FPV_EINVAL, "n must be positive");
+    FpvDepthK K;
+    FpvObjects T;
+    int rc = depth_constants(s, &K, &T);
+    if (rc != FPV_OK) return rc;
+    rc = depth_image_checks(s);
+    if (rc != FPV_OK) return rc;
+    const fpv_gate_v4* const gates = reinterpret_cast<const fpv_gate_v4*>(s->gate_descriptors);
+    for (int64_t i = 0; i < n; ++i) {
+        FpvQuat a; a.w = q[4 * i]; a.x = q[4 * i + 1]; a.y = q[4 * i + 2]; a.z = q[4 * i + 3];
+        const FpvRot R = fpv_rot(a);
+        float ox, oy, oz;
+        fpv_depth_origin(K, R, p[3 * i], p[3 * i + 1], p[3 * i + 2], &ox, &oy, &oz);
+        uint32_t obj_mask = 0u;
+        uint64_t gate_mask = 0ull;
+        for (int k = 0; k < T.count; ++k) obj_mask |= fpv_depth_object_near(K, T, k, ox, oy, oz) ? 1u << k : 0u;
+        for (int g = 0; g < K.gate_count; ++g)
+            gate_mask |= fpv_depth_gate_near(K, gates[(size_t)g * FPV_GATE_GROUPS], gates[(size_t)g * FPV_GATE_GROUPS + 3], ox, oy, oz) ? 1ull << g : 0ull;
+        for (int32_t y = 0; y < K.height; ++y)
+            for (int32_t x = 0; x < K.width; ++x) {
+                const float d = fpv_depth_pixel(K, T, gates, R, ox, oy, oz, obj_mask, gate_mask, (uint32_t)x, (uint32_t)y);
+                const int64_t at = i * s->image_stride + (int64_t)y * K.width + x;
+                if (s->encoding == FPV_DEPTH_U8) static_cast<uint8_t*>(s->image)[at] = (uint8_t)fpv_depth_u8(d, K.max_depth);
+                else static_cast<float*>(s->image)[at] = d;
+            }
     }
     return FPV_OK;
 }

@@ -206,6 +206,13 @@ class _Handle:
         if rc < 0:
             _lib.check(rc)
 
+    def _depth_render_raw(self, render: "_lib.FpvDepthRender", stream: Optional[torch.cuda.Stream] = None) -> None:
+        """One fpv_depth_render of this handle's drones on `stream` (None: torch's current stream): the state, the step counter
+        and the rotation of the traversal are left alone."""
+        rc = self._L.fpv_depth_render(self._handle, self._buf_ref, C.byref(render), self._stream() if stream is None else stream.cuda_stream)
+        if rc < 0:
+            _lib.check(rc)
+
     def _widen(self, cols: int) -> torch.Tensor:
         """fp16 storage decoded into a fresh float32 [14, cols] tensor: one launch of fpv_widen_state on torch's current stream,
         a copy valid for as long as the caller keeps it."""
@@ -224,7 +231,7 @@ class _Batch(_Handle):
                  with_action_out: bool = False, kahan_position: bool = False, per_drone_reset_pose: bool = False,
                  per_drone_physics: bool = False, gates: Any = None, laps: int = 0, gate_rewards: Optional[Dict[str, float]] = None,
                  miss_is_done: bool = False, gate_obs: bool = True, gate_start: Any = None, range_rays: Any = None,
-                 range_max: float = 20.0):
+                 range_max: float = 20.0, depth_camera: Any = None):
         if num_envs <= 0:
             raise ValueError("num_envs must be positive")
         device = torch.device(device)
@@ -301,6 +308,16 @@ class _Batch(_Handle):
             self.range_rows = torch.zeros((self.range_rays.shape[0], self.ld), **f32)
             self._scan = _lib.pack_range_scan(self.range_rays, range_max)
             self._scan.ranges, self._scan.ranges_ld = self.range_rows.data_ptr(), self.ld
+        # the depth camera (fpv_depth_render): `depth_camera` a fpyv_amd.camera.DepthCamera, `depth` [num_envs, H, W] float32 or
+        # uint8 the images a render writes - caller-visible, zero-copy, an output: checkpoints do not carry them
+        self.depth_camera = self.depth = self._render = None
+        self._render_objects = self._render_object_rows = None
+        if depth_camera is not None:
+            self.depth_camera = depth_camera
+            self._render = depth_camera.derive()
+            w, h = depth_camera.resolution
+            self.depth = torch.zeros((self.n, h, w), dtype=torch.uint8 if depth_camera.encoding == "u8" else torch.float32, device=self.device)
+            self._render.image, self._render.image_stride = self.depth.data_ptr(), w * h
         self._objects = None            # the bound fpv_objects_t (None = no collision world bound)
         self._object_rows = None
         self._override_keep = None
@@ -665,6 +682,37 @@ class _Batch(_Handle):
         """[R, num_envs] view of the range rows as the last scan wrote them (`.T`: the [num_envs, R] block of an observation)"""
         return None if self.range_rows is None else self.range_rows[:, :self.n]
 
+    # -- depth camera ------------------------------------------------------------------------------
+    def _render_world(self, object_list) -> None:
+        """The object list and the gates of the next render: a given list is converted as `step` converts it into the render's
+        own table; None takes what `set_objects` or the last `step` bound.  A batch with a bound course passes its own descriptor
+        table: gates that `set_gates` moved are seen where they are."""
+        if self._render is None:
+            raise ValueError("this batch was built without depth_camera=")
+        r = self._render
+        course = getattr(self, "_course", None)
+        r.gate_count = int(course.count) if course is not None else 0
+        r.gate_descriptors = self.gate_desc.data_ptr() if course is not None else None
+        if object_list is None:
+            r.objects = self._buf.objects
+            return
+        from .objects import to_rows
+        rows = to_rows(object_list)
+        if rows != self._render_object_rows or self._render_objects is None:  # a world that did not move is not re-packed
+            self._render_objects = _lib.pack_objects(rows)
+            self._render_object_rows = rows
+        r.objects = C.addressof(self._render_objects)
+
+    def render_depth(self, object_list=None) -> torch.Tensor:
+        """One image per drone on torch's current stream: what the drone's `depth_camera` sees of the Ground / Cylinder / Target
+        entries of `object_list` and of the batch's gate course - per pixel the z-depth of the nearest one, at most the camera's
+        `max_depth`; 0 from inside an object.  Returns `depth` [num_envs, H, W].  The render reads the position and the attitude
+        only: state, rewards, the step counter and the rotation of the traversal are what they were (include/fpv_abi.h "Depth
+        camera")."""
+        self._render_world(object_list)
+        self._depth_render_raw(self._render)
+        return self.depth
+
     def set_done_bits_target(self, target: Any = None, stride_words: int = 0) -> None:
         """Where the kernel writes the bit-packed done mask (one wave ballot per 64 drones):
         an int64 tensor of at least ceil(num_envs / 64) words or a raw device address; None restores the
@@ -840,6 +888,10 @@ class _Partition(_Handle):
         if self.parent._scan is not None:              # the parent's ray set on this partition's columns of the range rows
             self._scan = _lib.FpvRangeScan.from_buffer_copy(self.parent._scan)
             self._scan.ranges = self.parent._scan.ranges + 4 * lo
+        self._render = None
+        if self.parent._render is not None:            # the parent's camera on this partition's rows of the one image tensor
+            r = self._render = _lib.FpvDepthRender.from_buffer_copy(self.parent._render)
+            r.image = self.parent._render.image + lo * r.image_stride * self.parent.depth.element_size()
 
 
 def partition_bounds(n: int, parts: int) -> Sequence[Tuple[int, int]]:
@@ -1108,13 +1160,18 @@ class FpvVecEnv:
 
     def __init__(self, params: Optional[DroneParams] = None, num_envs: int = 1, device: Any = "cuda:0",
                  mode: str = "drone", auto_reset: bool = True, track_episodes: bool = True,
-                 wind: Sequence[float] = (0.0, 0.0, 0.0), object_list=(), partitions: int = 1, **batch_options: Any):
+                 wind: Sequence[float] = (0.0, 0.0, 0.0), object_list=(), partitions: int = 1, depth_every: int = 1,
+                 **batch_options: Any):
         """`batch_options` go to DroneBatch / RacerBatch (stick_noise=, noise_seed=, drone_id_offset=,
         fp16_state=, with_obs_aos=, kahan_position=, with_done_bits=, per_drone_physics=, ...); `object_list` is the
         collision world of every step (fpyv_amd.objects); `partitions` > 1 enables step_async / step_wait.  `range_rays=`
         (with `range_max=`) adds the range sensor: every step - and reset() - is followed by a scan of `object_list` on the same
         stream, `ranges` [R, num_envs] and info["ranges"] hold the result (a lane that auto-reset reports its reset pose's
-        ranges, like `obs`)."""
+        ranges, like `obs`).  `depth_camera=` (a fpyv_amd.camera.DepthCamera) adds the depth camera: reset() and every
+        `depth_every`-th step are followed by a render of `object_list` and the gate course on the same stream (each partition
+        into its rows of the one tensor), `depth` [num_envs, H, W] and info["depth"] hold the result; `depth_every=0` never renders
+        by itself - call `render_depth()`.  With `depth_every=1` the image always belongs to `obs`: a lane that auto-reset shows
+        its reset pose."""
         if mode not in ("drone", "racer"):
             raise ValueError(f'mode must be "drone" or "racer", got {mode!r}')
         params = params if params is not None else load_params(fps=1000)
@@ -1127,6 +1184,9 @@ class FpvVecEnv:
         self.num_envs = self.batch.n
         self.wind = tuple(float(w) for w in wind)
         self.object_list = list(object_list)
+        if int(depth_every) < 0:
+            raise ValueError("depth_every must be >= 0")
+        self.depth_every = int(depth_every)
         self.obs_dim = 13
         self.action_dim = 4
         self._obs_view = None
@@ -1189,6 +1249,7 @@ class FpvVecEnv:
         if not self._parts:
             self.batch.reset(mask=mask, **kw)
             self._range_scan(self.batch)
+            self._depth_after_reset()
             return self.obs
         cur = self._caller_waits_for_partitions()      # steps still in flight on the partitions' streams finish first
         if self.batch._cparams.flags & _lib.FPV_FLAG_RESET_JITTER:
@@ -1196,6 +1257,7 @@ class FpvVecEnv:
             self.batch.set_step_counter(min(P._steps_launched for P in self._parts))
         self.batch.reset(mask=mask, **kw)              # (the step counters run on, as the unpartitioned batch's does across a reset)
         self._range_scan(self.batch)
+        self._depth_after_reset()
         self._partitions_wait_for(cur)
         return self.obs
 
@@ -1234,6 +1296,44 @@ class FpvVecEnv:
         stepper._scan.objects = b._scan.objects
         stepper._range_scan_raw(stepper._scan, stream)
 
+    @property
+    def depth(self) -> Optional[torch.Tensor]:
+        """[num_envs, H, W] the depth images after the last render (None without depth_camera=): float32 metres or uint8"""
+        return self.batch.depth
+
+    def _depth_render(self, stepper: _Handle, stream: Optional[torch.cuda.Stream] = None) -> None:
+        """The depth camera after a step or a reset of `stepper` (the batch, or a partition on its own stream): the env's
+        collision world and the batch's course, the rows of `stepper`."""
+        b = self.batch
+        if b.depth is None:
+            return
+        b._render_world(self.object_list)
+        r = stepper._render
+        r.objects, r.gate_count, r.gate_descriptors = b._render.objects, b._render.gate_count, b._render.gate_descriptors
+        stepper._depth_render_raw(r, stream)
+
+    def _depth_after_reset(self) -> None:
+        """a reset() is followed by a render of the whole population (unless depth_every = 0) and restarts the count of steps"""
+        for stepper in [self.batch] + self._parts:
+            stepper._depth_steps = 0
+        if self.depth_every:
+            self._depth_render(self.batch)
+
+    def _depth_after_step(self, stepper: _Handle, stream: Optional[torch.cuda.Stream] = None) -> None:
+        """every `depth_every`-th step of `stepper` since the last reset() is followed by a render"""
+        if self.batch.depth is None or self.depth_every == 0:
+            return
+        k = stepper._depth_steps = getattr(stepper, "_depth_steps", 0) + 1
+        if k % self.depth_every == 0:
+            self._depth_render(stepper, stream)
+
+    def render_depth(self) -> torch.Tensor:
+        """Render every drone's image now, on the caller's stream, ordered after steps in flight like reset; returns `depth`."""
+        if self.batch.depth is None:
+            raise ValueError("this env was built without depth_camera=")
+        self._whole_population(self._depth_render, self.batch)
+        return self.batch.depth
+
     def _whole_population(self, fn, *a, **kw) -> None:
         if not self._parts:
             fn(*a, **kw)
@@ -1255,6 +1355,7 @@ class FpvVecEnv:
         self._bind_world(self.batch)
         self.batch._step_raw(action)
         self._range_scan(self.batch)
+        self._depth_after_step(self.batch)
         return self.obs, self.batch.reward, self.batch.done, self._info(self.batch, 0, self.num_envs)
 
     def _bind_world(self, stepper: _Handle) -> None:
@@ -1278,6 +1379,8 @@ class FpvVecEnv:
             info["gates_passed"], info["gate_event"] = (w >> 10) & 0x3FFFFF, (w >> 8) & 3
         if getattr(batch, "range_rows", None) is not None:             # the range sensor: [R, columns] after this step's scan
             info["ranges"] = batch.range_rows[:, lo:hi]
+        if getattr(batch, "depth", None) is not None:                  # the depth camera: [columns, H, W] after the last render
+            info["depth"] = batch.depth[lo:hi]
         return info
 
     # -- split phase ------------------------------------------------------------------------------
@@ -1314,6 +1417,7 @@ class FpvVecEnv:
         self._bind_world(P)
         P._step_raw(action, stream=P.stream)
         self._range_scan(P, P.stream)
+        self._depth_after_step(P, P.stream)
 
     def step_wait(self, part: int, sync: bool = True) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor, Dict[str, Any]]:
         """(obs, reward, done, info) of partition `part` - views of its columns - ordered after its last enqueued step:

@@ -314,7 +314,7 @@ typedef struct fpv_env* fpv_handle_t;
 
 int fpv_abi_version(void);
 /* sizeof of the ABI structs as this library was compiled (0 fpv_params_t, 1 fpv_buffers_t, 2 fpv_objects_t,
- * 3 fpv_pid_params_t, 4 fpv_cache_model_t, 5 fpv_gate_course_t):
+ * 3 fpv_pid_params_t, 4 fpv_cache_model_t, 5 fpv_gate_course_t, 6 fpv_range_scan_t, 7 fpv_depth_render_t):
  * lets a foreign-language binding verify its struct declarations at load time */
 int fpv_sizeof(int which);
 /* rows of the state matrix for a mode (FPV_DRONE_ROWS / FPV_RACER_ROWS), or FPV_EINVAL */
@@ -537,8 +537,8 @@ int fpv_gate_eval(const fpv_gate_course_t* course, int64_t n, const float* p_old
                   const uint8_t* physics_done, const uint32_t* word_in, int auto_reset, const float* p_after, const float* q_after,
                   uint32_t* word_out, float* reward, uint8_t* done, float* obs);
 
-/* ---- Range scan: body-frame ray distances to the object list (build-defined; the reference's Camera over point clouds is out
- * of scope) ----------------------------------------------------------------------------------------------------------------
+/* ---- Range scan: body-frame ray distances to the object list (build-defined; the reference's rendering of point clouds is out
+ * of scope; the depth camera is "Depth camera" below) ------------------------------------------------------------
  * A ray set is 1..FPV_MAX_RAYS unit directions d_b in the body frame.  The ray r of drone i starts at its position p_i and runs
  * along d = R(q_i) d_b (body -> world, not renormalised); a range is the parameter t along d.  Every object of the list is a
  * convex solid in the geometry the collisions use - Ground the half-space z <= 0, Cylinder (x-ob.x)^2 + (y-ob.y)^2 <= radius^2
@@ -546,7 +546,7 @@ int fpv_gate_eval(const fpv_gate_course_t* course, int64_t n, const float* p_old
  * when t_in <= t_out and t_out >= 0, at range max(t_in, 0) (0 from inside).  ranges[r][i] = min(max_range, nearest hit); a ray
  * that hits nothing, an empty or NULL list: max_range.  Rays parallel to a constraint (|d_z| < 1e-12 for the ground and a
  * cylinder's caps, d_x^2 + d_y^2 < 1e-24 for its wall) satisfy it always or never; no input gives a NaN.  Gates and trails are
- * not seen.  ONE definition (csrc/fpv_range.h fpv_range_lane) is run by the kernel (csrc/fpv_range.hip) and by fpv_range_eval on
+ * not seen by the scan (the depth camera sees gates).  ONE definition (csrc/fpv_range.h fpv_range_lane) is run by the kernel (csrc/fpv_range.hip) and by fpv_range_eval on
  * the host: the same bits.  The scan is a kernel of its own: it serves every fp32 handle (drone or Racer; a physics table, a gate
  * course, stick noise, reset sources, partitions), leaves the state, the step counter and the rotation of the traversal alone,
  * and moves 28 + 4 ray_count bytes per drone. */
@@ -573,6 +573,64 @@ int fpv_range_scan(fpv_handle_t h, const fpv_buffers_t* b, const fpv_range_scan_
 /* The kernel's own lane function on the host (no handle, no device): drone i of n at p[i][3] with attitude q[i][4] (wxyz);
  * s->ranges is HOST memory. */
 int fpv_range_eval(const fpv_range_scan_t* s, int64_t n, const float* p /*[n][3]*/, const float* q /*[n][4] wxyz*/);
+
+/* ---- Depth camera: one depth image per drone of the object list and the gates (the reference's Camera, components.py:449-629) ----
+ * The camera is the reference's Camera(camera_pitch_angle, position_relative_to_frame, [W, H], fov): f = W / (2 tan(fov / 2)),
+ * cx = W / 2, cy = H / 2, rel_rot = WORLD2CAM^T euler_angles_to_rotation_matrix(deg2rad(pitch), 0, 0) (the pitch goes in as the roll:
+ * a rotation about x after the axis swap - reproduced as computed), origin o = p + R(q) rel_pos, rotation C = R(q) rel_rot.  Pixel
+ * (i, j) = column i, row j looks along d = R(q) rel_rot ((i + 1/2 - cx) / f, (j + 1/2 - cy) / f, 1) - not normalised: its
+ * camera-frame z is 1, so the ray parameter IS the reference's depth (the third row of projection_matrix @ point, a z-depth).
+ * image[drone][j][i] = min(max_depth, nearest hit); nothing hit: max_depth.  Where the reference splats point clouds the
+ * semantics are this build's: objects are exactly the range scan's solids and hit rule (0 from inside), and GATES ARE SEEN - a gate
+ * is a zero-thickness plate in its plane, seen from both faces: the region inside the aperture grown by gate_frame_width and
+ * outside the aperture itself (descriptor rows of fpv_gates_derive; csrc/fpv_depth.h has the exact tests).  No input gives a NaN.
+ * ONE definition (csrc/fpv_depth.h fpv_depth_pixel) is run by the kernel (csrc/fpv_depth.hip: a lane is a pixel, a wave 64
+ * consecutive pixels of one drone) and by fpv_depth_eval on the host: the same bits.  Like the range scan the render is a kernel
+ * of its own that reads p and q only: it serves every fp32 handle and leaves the state, the step counter and the rotation alone. */
+#define FPV_DEPTH_MAX_SIDE 128
+enum { FPV_DEPTH_METRES = 0,   /* fp32 metres */
+       FPV_DEPTH_U8 = 1 };     /* the reference's image byte (uint8)(255 (1 - depth / max_depth)), truncated, computed in fp32 */
+typedef struct fpv_camera {          /* what fpv_camera_derive reads: the reference's Camera arguments */
+    double pitch_deg;                /* camera_pitch_angle */
+    double relative_position[3];     /* position_relative_to_frame, body frame, m */
+    double fov_deg;                  /* in (0, 180) */
+    int32_t width, height;           /* resolution [W, H]: 4..FPV_DEPTH_MAX_SIDE each, W a multiple of 4 */
+} fpv_camera_t;
+typedef struct fpv_depth_render {
+    uint32_t struct_size;            /* sizeof(fpv_depth_render_t) = fpv_sizeof(7) */
+    int32_t  width, height;          /* written by fpv_camera_derive */
+    int32_t  encoding;               /* FPV_DEPTH_METRES / FPV_DEPTH_U8 */
+    float    dir0[3], dir_u[3], dir_v[3];   /* body-frame direction of pixel (i, j) = dir0 + i dir_u + j dir_v (fpv_camera_derive) */
+    float    offset[3];              /* the camera's position in the body frame (fpv_camera_derive) */
+    float    dir_len_max;            /* sqrt(1 + (W / 2f)^2 + (H / 2f)^2), rounded up: no pixel's direction is longer (fpv_camera_derive) */
+    float    max_depth;              /* finite, > 0 */
+    float    gate_frame_width;       /* finite, > 0 (read only with gates) */
+    int32_t  gate_count;             /* 0..FPV_MAX_GATES */
+    double   focal_length;           /* informational, written by fpv_camera_derive: the reference's focal_length ...       */
+    double   relative_rotation[9];   /* ... and relative_rotation_matrix, row-major, in double                              */
+    void*    image;                  /* [n][image_stride] elements (fp32 or bytes), row-major [H][W] inside; write-only; DEVICE for
+                                        fpv_depth_render, HOST for fpv_depth_eval; 4-byte aligned */
+    int64_t  image_stride;           /* elements per drone: >= W * H, multiple of 4; the padding is not written */
+    const fpv_objects_t* objects;    /* host memory, read during the call; NULL or count 0: no objects */
+    const float* gate_descriptors;   /* [gate_count][FPV_GATE_FLOATS] as fpv_gates_derive wrote them, 16-byte aligned: DEVICE for
+                                        fpv_depth_render (the table fpv_set_gates binds: moving gates are seen where they are), HOST
+                                        for fpv_depth_eval; not read with gate_count 0 */
+} fpv_depth_render_t;
+/* Fills width, height, dir0, dir_u, dir_v, offset, dir_len_max, focal_length and relative_rotation of *out (host arithmetic only;
+ * every other field is left alone).  FPV_EPARAM, by name: width or height outside 4..128, width not a multiple of 4, fov outside
+ * (0, 180), a pitch or a relative position that is not finite. */
+int fpv_camera_derive(const fpv_camera_t* camera, fpv_depth_render_t* out);
+/* One image per drone of the handle at b->state / b->ld on `stream`, under the handle's device: allocates nothing, never
+ * synchronises, does not advance the step index and does not touch the rotation.  FPV_EINVAL / FPV_EALIGN, by name: fp16 state
+ * (the packed quaternion has no reader here - the follow-up the range scan names), a wrong struct_size, width or height outside
+ * 4..128 or width not a multiple of 4, an unknown encoding, direction vectors that are not finite, image_stride < W * H or not a
+ * multiple of 4, max_depth (or, with gates, gate_frame_width) not finite or not positive, a null or misaligned image, more than
+ * FPV_MAX_OBJECTS objects or an unknown object type, gate_count outside 0..FPV_MAX_GATES, gates without descriptors, more than
+ * 2^31 waves in all; and in a library built without csrc/fpv_depth.hip. */
+int fpv_depth_render(fpv_handle_t h, const fpv_buffers_t* b, const fpv_depth_render_t* s, void* stream);
+/* The kernel's own pixel function on the host (no handle, no device): drone i of n at p[i][3] with attitude q[i][4] (wxyz);
+ * s->image and s->gate_descriptors are HOST memory. */
+int fpv_depth_eval(const fpv_depth_render_t* s, int64_t n, const float* p /*[n][3]*/, const float* q /*[n][4] wxyz*/);
 
 /* Row stride (in floats) to allocate for n drones.  Up to 2^18 drones: n rounded up to 64, padded so that the stride in
  * bytes is at least 1 KiB past a multiple of 8 KiB (strides at or near a multiple of 8 KiB put all 14
