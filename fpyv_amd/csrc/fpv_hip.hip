@@ -45,6 +45,7 @@ template <bool NOISE = false, bool OBJ = false, bool KAHAN = false, bool OVR = f
 __global__ __launch_bounds__(kStepBlock) FPV_EXP_STEP_ATTR void fpv_drone_step_kernel(FPV_STEP_PARAMS)
 {
     constexpr bool SECTIONED = NOISE || (OBJ && OVR);
+    constexpr bool PLAIN = !NOISE && !OBJ && !KAHAN && !OVR;
     FPV_STEP_VIEW;
     __shared__ FpvNormalRow ntab[NOISE ? FPV_NTAB_ROWS : 1];
     if (NOISE) stage_normal_table(ntab);
@@ -56,6 +57,22 @@ __global__ __launch_bounds__(kStepBlock) FPV_EXP_STEP_ATTR void fpv_drone_step_k
     float ro[9] = {1.f, 0.f, 0.f, 0.f, 1.f, 0.f, 0.f, 0.f, 1.f}, to = 0.0f;
     // ---- 1. issue every load of this lane before the first use; the sticks
     float4 a = (!NOISE || B.action) ? ld_action_any(B.action, B.action_ld, i) : make_float4(0.f, 0.f, 0.f, 0.f);
+    // The plain kernel issues the scalar loads of its constants and of the wind HERE, ahead of the 14 row loads, through one
+    // view of the arguments: they are then in flight together with the rows, and the wait for them stands after the last row
+    // load as before.  Under the rotated traversal the first generation of waves finds its rows in the L2s and used to wait
+    // for constants whose loads went out only after the rows'.  A/B in one process at 2^20 drones (profiles/const_block.md):
+    // 19.75 against 20.04 us per launch rotated, 22.35 against 22.61 in the plain order; twins of one build differ by 0.005.
+    // The wind goes out AFTER the constants: ahead of them, the dead fourth dword of its dwordx4 load is a register that a
+    // constant load then takes, and the hazard costs a wait for every scalar load in front of the row loads.
+    const FpvStepArgs* T = nullptr;
+    float wind[3] = {0.f, 0.f, 0.f};
+    FpvK Kt;
+    if (PLAIN) {
+        T = &fpv_step_args_again();
+        Kt = T->K;
+        wind[0] = T->B.wx; wind[1] = T->B.wy; wind[2] = T->B.wz;
+        __builtin_amdgcn_sched_barrier(0);
+    }
     ld_drone(B.state, B.ld, i, s);
     if (NOISE) a = apply_stick_noise(K, B, i, a, ntab);
     if (OVR) {
@@ -63,21 +80,21 @@ __global__ __launch_bounds__(kStepBlock) FPV_EXP_STEP_ATTR void fpv_drone_step_k
         for (int k = 0; k < 9; ++k) ro[k] = B.rot_over[(int64_t)i * 9 + k];     // 64-bit index: 36 * i can pass 2^32
         to = B.thrust_over[i];
     }
-    // keep every vector load ahead of the scalar (kernarg) loads of the physics constants: without
-    // this fence the compiler parks the last four row loads behind an s_waitcnt on those constants
-    // (+1.4 % per launch, A/B in one process)
+    // no vector load waits behind a scalar load: without this fence the compiler parks the last four row loads behind an
+    // s_waitcnt on the constants (+1.4 % per launch, A/B in one process, plain order, rounds 1-3).  The other instantiations
+    // still load their constants after it; only the plain kernel's order has been measured under the rotation.
     __builtin_amdgcn_sched_barrier(0);
     // ---- 2. the physics, on its own view of the constants when SECTIONED
     const FpvStepArgs* P = nullptr;
-    if (SECTIONED) P = &fpv_step_args_again();             // (the opaque view is a volatile asm: not even emitted for the plain kernel)
-    const FpvK& Kp = SECTIONED ? P->K : K;
+    if (SECTIONED) P = &fpv_step_args_again();
+    const FpvK& Kp = SECTIONED ? P->K : PLAIN ? Kt : K;
     const FpvBufD& Bp = SECTIONED ? P->B : B;
     float kc[6];
     if (KAHAN) {
 #pragma unroll
         for (int k = 0; k < 6; ++k) kc[k] = row_at(ROW(Bp.pos_comp, k, a_ld), i);
     }
-    const FpvStepOut o = fpv_drone_step_lane<OBJ>(Kp, s, a.x, a.y, a.z, a.w, Bp.wx, Bp.wy, Bp.wz, &B_.objs,   // the table stays in the kernarg segment (a local copy of an indexed array would live in scratch)
+    const FpvStepOut o = fpv_drone_step_lane<OBJ>(Kp, s, a.x, a.y, a.z, a.w, PLAIN ? wind[0] : Bp.wx, PLAIN ? wind[1] : Bp.wy, PLAIN ? wind[2] : Bp.wz, &B_.objs,   // the table stays in the kernarg segment (a local copy of an indexed array would live in scratch)
                                                   KAHAN ? kc : nullptr, OVR ? ro : nullptr, to);
     // ---- 3. the stores
     // OBJ: the store addresses are formed only now - the 14 row-address pairs the compiler would otherwise carry from
@@ -87,7 +104,7 @@ __global__ __launch_bounds__(kStepBlock) FPV_EXP_STEP_ATTR void fpv_drone_step_k
     if (OBJ || SECTIONED) FPV_KEEP_HERE(j);
     const FpvStepArgs* E = nullptr;
     if (SECTIONED) E = &fpv_step_args_again();
-    const FpvK& Ke = SECTIONED ? E->K : K;
+    const FpvK& Ke = SECTIONED ? E->K : PLAIN ? Kt : K;
     FpvBufD Bs = B;
     if (SECTIONED) { Bs = E->B; Bs.state = E->state; Bs.ld = E->ld; }
     const FpvBufD& Be = Bs;

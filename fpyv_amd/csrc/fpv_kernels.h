@@ -306,7 +306,7 @@ __device__ __forceinline__ FpvBufD fpv_step_view(const FpvBufD& B_, float* st, i
 // Philox keys and the table staging on top of the physics constants and a dozen buffer pointers; object list + guidance
 // override) read their arguments once per SECTION - loads and sticks / physics / stores - instead of keeping every field
 // alive from the first instruction to the last: 12-34 spilled SGPRs (v_readlane / v_writelane per use) in round 3,
-// none now.  The plain kernel keeps the direct form: it never spilled and is the measured optimum as it stands.
+// none now.  The plain kernel takes one view, for its constants and the wind, ahead of its row loads (fpv_drone_step_kernel).
 struct FpvStepArgs { float* state; int64_t ld; const float4* action; int64_t action_ld; uint16_t* state_h; int64_t n; FpvK K; FpvBufD B; };
 __device__ __forceinline__ const FpvStepArgs& fpv_step_args_again()
 {

@@ -22,6 +22,7 @@ VARIANTS = {
     # how a lane of the gate kernels reaches its gate's descriptor row (csrc/fpv_gate.hip; time with --gates): per-lane gather from
     # global memory / the workgroup's LDS copy of the table
     "gategl": ["-DFPV_EXP_GATE_LDS=0"], "gatelds": ["-DFPV_EXP_GATE_LDS=1"],
+    "base2": [],       # A/A: a second copy of the shipped build - what two handles of one process differ by (profiles/const_block.md)
     "pre12": ["PRELOAD=12"], "pre16": ["PRELOAD=16"], "pre8": ["PRELOAD=8"],       # kernel-argument dwords preloaded into SGPRs (shipped: 6 = state, ld, action; 12 reaches n_start)
 }
 ap = argparse.ArgumentParser()
