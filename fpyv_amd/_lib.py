@@ -115,6 +115,21 @@ def pack_objects(objects) -> FpvObjects:
     return t
 
 
+class ObjectTable:
+    """The fpv_objects_t of an object_list that is given again and again: `address(object_list)` converts the list as `step` does
+    (objects.to_rows: `rows`) and packs it only when the rows are not the last call's - a world that did not move is not re-packed."""
+
+    def __init__(self):
+        self.rows = self.packed = None
+
+    def address(self, object_list) -> int:
+        from .objects import to_rows
+        rows = to_rows(object_list)
+        if rows != self.rows:
+            self.packed, self.rows = pack_objects(rows), rows
+        return C.addressof(self.packed)
+
+
 class FpvBuffers(C.Structure):
     _fields_ = [
         ("state", C.c_void_p), ("ld", C.c_int64), ("action", C.c_void_p), ("reward", C.c_void_p),

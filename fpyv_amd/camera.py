@@ -12,6 +12,8 @@ from typing import Any, Sequence
 import numpy as np
 
 from . import _lib
+from .objects import to_rows
+from .rays import poses
 
 
 class DepthCamera:
@@ -84,12 +86,8 @@ class DepthCamera:
         """fpv_depth_eval: the render kernel's own pixel function on the host, for n drones at once.  p [n, 3], q [n, 4] (wxyz),
         `object_list` what `step` takes (or raw rows), `gates` a list of gates or their [count, 16] descriptor rows
         (`fpyv_amd.gates.derive`).  Returns the images [n, H, W], float32 or uint8."""
-        from .objects import to_rows
-        f32 = lambda a, w: np.ascontiguousarray(np.asarray(a, dtype=np.float32).reshape(-1, w))  # noqa: E731
-        pp, qq = f32(p, 3), f32(q, 4)
+        pp, qq = poses(p, q)
         n = pp.shape[0]
-        if qq.shape[0] != n:
-            raise ValueError("p and q must describe the same n drones")
         s = self.derive()
         objs = _lib.pack_objects(to_rows(object_list or ()))
         s.objects = C.addressof(objs)

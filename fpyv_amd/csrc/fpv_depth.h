@@ -2,8 +2,8 @@
 // depth image reports.  fpv_depth_pixel below is what every lane of the gfx950 kernel of fpv_depth.hip runs for its pixel and what
 // fpv_depth_eval (fpv_hip.hip, host) runs: the same operations in the same order on the same fp32 values - explicit fmaf,
 // fpv_sqrt_flushed, plain '/', compare-and-select instead of fmaxf / fminf, no libm call, -ffp-contract=off - so the host
-// reproduces the kernel's images bit for bit.  The ray, the half-space, the slab and the round solids are fpv_range.h's own
-// functions (included, not changed).
+// reproduces the kernel's images bit for bit.  Everything about the solids is fpv_range.h's own: the ray, the per-object body
+// (fpv_range_solid), the hit rule (fpv_range_nearer) and the near test of the cull (fpv_range_near) - called here, defined there.
 //
 // Camera.  The reference's Camera(camera_pitch_angle, position_relative_to_frame, [W, H], fov): f = W / (2 tan(fov / 2)),
 // cx = W / 2, cy = H / 2, rel_rot = WORLD2CAM^T Rx(pitch) = [[0, s, c], [1, 0, 0], [0, -c, s]] (s, c = sin, cos of the pitch: the
@@ -74,9 +74,7 @@ FPV_HD void fpv_depth_origin(const FpvDepthK& K, const FpvRot& R, float px, floa
 // the cull of object k (k < T.count) for a camera at o
 FPV_HD bool fpv_depth_object_near(const FpvDepthK& K, const FpvObjects& T, int k, float ox, float oy, float oz)
 {
-    const float* c = K.near[k];
-    const float ux = ox - c[0], uy = oy - c[1], uz = oz - c[2];
-    return T.o[k].type == 0 ? oz < c[3] : fmaf(ux, ux, fmaf(uy, uy, uz * uz)) < c[3] * c[3];
+    return fpv_range_near(K.near[k], T.o[k].type, ox, oy, oz);
 }
 
 // the cull of the gate whose first and last 16-byte groups are g0 (c.x c.y c.z n.x) and g3 (a hz zc r2)
@@ -108,20 +106,7 @@ FPV_HD float fpv_depth_pixel(const FpvDepthK& K, const FpvObjects& T, P gates, c
     // ---- the objects: uniform trip count, only predicates differ between lanes
     for (int k = 0; k < T.count; ++k) {
         if (!((obj_mask >> k) & 1u)) continue;
-        const FpvObject& ob = T.o[k];
-        FpvInterval I;
-        if (ob.type == 0) {
-            I = fpv_range_below(y, oz, 0.0f);
-        } else if (ob.type == 1) {
-            I = fpv_range_round<false>(y, ob.x - ox, ob.y - oy, 0.0f, ob.radius);
-            const FpvInterval Z = fpv_range_slab(y, oz, ob.z, ob.z + ob.height);
-            I.t_in = fpv_sel_max(I.t_in, Z.t_in); I.t_out = fpv_sel_min(I.t_out, Z.t_out);
-        } else {
-            I = fpv_range_round<true>(y, ob.x - ox, ob.y - oy, ob.z - oz, ob.radius);
-        }
-        const bool hit = I.t_in <= I.t_out && I.t_out >= 0.0f;
-        const float t = fpv_sel_max(I.t_in, 0.0f);
-        best = (hit && t < best) ? t : best;
+        best = fpv_range_nearer(fpv_range_solid(y, ox, oy, oz, T.o[k]), true, best);
     }
     // ---- the gates the drone is near: the set bits of a uniform mask
     for (uint64_t m = gate_mask; m != 0ull; m &= m - 1ull) {

@@ -887,6 +887,61 @@ int check_combination(const fpv_env* h, Family f, const fpv_buffers_t* b)
                    {!table && (h->K.flags & FPV_FLAG_STICK_NOISE) && b->objects && b->objects->count > 0, "stick noise AND an object list (either one alone is served)"}});
 }
 
+// THE intake of an object list - the step's, a scan's, a render's - in three parts (check_buffers asks what the handle can serve
+// between the first two): the count (`most`: a sensor's refusal also says how many there may be), the types, and the rows of a
+// list that passed both in the kernels' form (*T comes zeroed; `has_ground`, `lo`, `hi` are the step's: fpv_objects_bounds).
+int check_object_count(const fpv_objects_t* in, bool most)
+{
+    if (in && (in->count < 0 || in->count > FPV_MAX_OBJECTS))
+        return fail(FPV_EINVAL, "objects.count out of range" + (most ? " (at most " + std::to_string(FPV_MAX_OBJECTS) + " objects)" : std::string()));
+    return FPV_OK;
+}
+
+int check_object_types(const fpv_objects_t* in)
+{
+    for (int k = 0; in && k < in->count; ++k)
+        if (in->obj[k].type < FPV_OBJ_GROUND || in->obj[k].type > FPV_OBJ_SPHERE) return fail(FPV_EINVAL, "unknown object type");
+    return FPV_OK;
+}
+
+void copy_objects(const fpv_objects_t* in, FpvObjects* T)
+{
+    if (!in) return;
+    T->count = in->count;
+    for (int k = 0; k < T->count; ++k) {
+        const fpv_object_t& o = in->obj[k];
+        T->o[k].type = o.type; T->o[k].x = o.x; T->o[k].y = o.y; T->o[k].z = o.z; T->o[k].radius = o.radius; T->o[k].height = o.height;
+    }
+}
+
+// What a scan and a render ask first, `sensor` named in the refusals: of the build (`kernel`: the weak lookup function of
+// csrc/`unit`.hip was linked - what a build without it answers to any call), then of the handle and the buffers.
+int check_sensor(const fpv_env* h, const fpv_buffers_t* b, const void* s, bool kernel, const std::string& sensor, const char* unit)
+{
+    if (!kernel) return fail(FPV_EINVAL, "the " + sensor + " is not in this build (the library was linked without csrc/" + unit + ".hip)");
+    if (!h) return fail(FPV_EINVAL, "null handle");
+    if (!b || !s) return fail(FPV_EINVAL, "null argument");
+    if (h->K.flags & FPV_FLAG_FP16_STATE)
+        return fail(FPV_EINVAL, "the " + sensor + " cannot read fp16 state (FPV_FLAG_FP16_STATE): a reader of the packed quaternion is the follow-up");
+    if (!b->state) return fail(FPV_EINVAL, "fpv_buffers_t.state is null");
+    if (b->ld < h->n) return fail(FPV_EALIGN, "fpv_buffers_t.ld is smaller than the number of drones");
+    return FPV_OK;
+}
+
+// What fpv_range_eval and fpv_depth_eval ask of their arguments first, and pose i of q [n][4] (wxyz)
+int check_eval_args(const void* s, int64_t n, const float* p, const float* q)
+{
+    if (!s || !p || !q) return fail(FPV_EINVAL, "null argument");
+    if (n <= 0) return fail(FPV_EINVAL, "n must be positive");
+    return FPV_OK;
+}
+
+FpvQuat pose_quat(const float* q, int64_t i)
+{
+    FpvQuat a; a.w = q[4 * i]; a.x = q[4 * i + 1]; a.y = q[4 * i + 2]; a.z = q[4 * i + 3];
+    return a;
+}
+
 int check_buffers(const fpv_env* h, const fpv_buffers_t* b, bool need_action)  // NOLINT
 {
     if (!h) return fail(FPV_EINVAL, "null handle");
@@ -912,13 +967,13 @@ int check_buffers(const fpv_env* h, const fpv_buffers_t* b, bool need_action)  /
     if (b->done_bits_stride && (b->done_bits_stride < (h->n + 63) / 64))
         return fail(FPV_EALIGN, "done_bits_stride must be 0 or >= ceil(n / 64) words");
     if (b->objects && b->objects->count != 0) {
-        if (b->objects->count < 0 || b->objects->count > FPV_MAX_OBJECTS) return fail(FPV_EINVAL, "objects.count out of range");
+        int rc = check_object_count(b->objects, false);
+        if (rc != FPV_OK) return rc;
         if (h->mode != FPV_MODE_DRONE || (h->K.flags & (FPV_FLAG_FP16_STATE | FPV_FLAG_GROUND)) || b->obs_aos)
             return fail(FPV_EINVAL, "objects need drone mode with fp32 state and cannot be combined with "
                                     "FPV_FLAG_GROUND (use a Ground entry) or obs_aos");
-        for (int k = 0; k < b->objects->count; ++k)
-            if (b->objects->obj[k].type < FPV_OBJ_GROUND || b->objects->obj[k].type > FPV_OBJ_SPHERE)
-                return fail(FPV_EINVAL, "unknown object type");
+        rc = check_object_types(b->objects);
+        if (rc != FPV_OK) return rc;
     }
     if (b->pos_comp) {
         if (h->mode != FPV_MODE_DRONE || (h->K.flags & FPV_FLAG_FP16_STATE) || b->obs_aos)
@@ -980,14 +1035,8 @@ FpvBufD to_device_view(const fpv_env* h, const fpv_buffers_t* b)
     d.action_ld = b->action_ld;
     d.rot_over = b->rotation_override; d.thrust_over = b->thrust_override;
     d.thrust_h = b->state_h_thrust ? b->state_h_thrust : (b->state_h ? b->state_h + (int64_t)2 * FPV_HALF_PAIR_ROWS * b->ld : nullptr);
-    d.objs.count = 0;
     if (b->objects) {
-        d.objs.count = b->objects->count;
-        for (int k = 0; k < d.objs.count && k < FPV_MAX_OBJECTS; ++k) {
-            const fpv_object_t& o = b->objects->obj[k];
-            d.objs.o[k].type = o.type; d.objs.o[k].x = o.x; d.objs.o[k].y = o.y; d.objs.o[k].z = o.z;
-            d.objs.o[k].radius = o.radius; d.objs.o[k].height = o.height;
-        }
+        copy_objects(b->objects, &d.objs);             // (check_buffers has passed the list)
         fpv_objects_bounds(d.objs, reach);
     }
     d.reset_pose = b->reset_pose;
@@ -1587,16 +1636,10 @@ int range_constants(const fpv_range_scan_t* s, FpvRangeK* K, FpvObjects* T)
         if (!(fabs(l2 - 1.0) <= 1.0e-4)) return fail(FPV_EINVAL, "ray " + std::to_string(r) + " is not a unit direction (rays come from fpv_rays_derive)");
         for (int j = 0; j < 3; ++j) K->rays[r][j] = d[j];
     }
-    if (s->objects && s->objects->count != 0) {
-        if (s->objects->count < 0 || s->objects->count > FPV_MAX_OBJECTS)
-            return fail(FPV_EINVAL, "objects.count out of range (at most " + std::to_string(FPV_MAX_OBJECTS) + " objects)");
-        T->count = s->objects->count;
-        for (int k = 0; k < T->count; ++k) {
-            const fpv_object_t& o = s->objects->obj[k];
-            if (o.type < FPV_OBJ_GROUND || o.type > FPV_OBJ_SPHERE) return fail(FPV_EINVAL, "unknown object type");
-            T->o[k].type = o.type; T->o[k].x = o.x; T->o[k].y = o.y; T->o[k].z = o.z; T->o[k].radius = o.radius; T->o[k].height = o.height;
-        }
-    }
+    int rc = check_object_count(s->objects, true);
+    if (rc == FPV_OK) rc = check_object_types(s->objects);
+    if (rc != FPV_OK) return rc;
+    copy_objects(s->objects, T);
     fpv_range_bounds(*T, K->max_range, K->near);
     return FPV_OK;
 }
@@ -1605,17 +1648,11 @@ int range_constants(const fpv_range_scan_t* s, FpvRangeK* K, FpvObjects* T)
 
 int fpv_range_scan(fpv_handle_t h, const fpv_buffers_t* b, const fpv_range_scan_t* s, void* stream)
 {
-    if (!fpv_range_scan_kernel_fn)        // (asked first: what a build without the kernel answers to any scan)
-        return fail(FPV_EINVAL, "the range scan is not in this build (the library was linked without csrc/fpv_range.hip)");
-    if (!h) return fail(FPV_EINVAL, "null handle");
-    if (!b || !s) return fail(FPV_EINVAL, "null argument");
-    if (h->K.flags & FPV_FLAG_FP16_STATE)
-        return fail(FPV_EINVAL, "the range scan cannot read fp16 state (FPV_FLAG_FP16_STATE): a reader of the packed quaternion is the follow-up");
-    if (!b->state) return fail(FPV_EINVAL, "fpv_buffers_t.state is null");
-    if (b->ld < h->n) return fail(FPV_EALIGN, "fpv_buffers_t.ld is smaller than the number of drones");
+    int rc = check_sensor(h, b, s, fpv_range_scan_kernel_fn != nullptr, "range scan", "fpv_range");
+    if (rc != FPV_OK) return rc;
     FpvRangeArgs A;
     memset(&A, 0, sizeof(A));
-    const int rc = range_constants(s, &A.K, &A.T);
+    rc = range_constants(s, &A.K, &A.T);
     if (rc != FPV_OK) return rc;
     if (!s->ranges) return fail(FPV_EINVAL, "fpv_range_scan_t.ranges is null");
     if ((uintptr_t)s->ranges & 3) return fail(FPV_EALIGN, "ranges must be 4-byte aligned");
@@ -1630,21 +1667,19 @@ int fpv_range_scan(fpv_handle_t h, const fpv_buffers_t* b, const fpv_range_scan_
 
 int fpv_range_eval(const fpv_range_scan_t* s, int64_t n, const float* p, const float* q)
 {
-    if (!s || !p || !q) return fail(FPV_EINVAL, "null argument");
-    if (n <= 0) return fail(FPV_EINVAL, "n must be positive");
+    int rc = check_eval_args(s, n, p, q);
+    if (rc != FPV_OK) return rc;
     FpvRangeK K;
     FpvObjects T;
-    const int rc = range_constants(s, &K, &T);
+    rc = range_constants(s, &K, &T);
     if (rc != FPV_OK) return rc;
     if (!s->ranges) return fail(FPV_EINVAL, "fpv_range_scan_t.ranges is null");
     if (s->ranges_ld < n) return fail(FPV_EALIGN, "ranges_ld is smaller than n");
     if (s->ranges_ld % 4) return fail(FPV_EALIGN, "ranges_ld must be a multiple of 4 floats");
     float* const out = s->ranges;
     const int64_t ld = s->ranges_ld;
-    for (int64_t i = 0; i < n; ++i) {
-        FpvQuat a; a.w = q[4 * i]; a.x = q[4 * i + 1]; a.y = q[4 * i + 2]; a.z = q[4 * i + 3];
-        fpv_range_lane(K, T, a, p[3 * i], p[3 * i + 1], p[3 * i + 2], [&](int r, float t) { out[(int64_t)r * ld + i] = t; });
-    }
+    for (int64_t i = 0; i < n; ++i)
+        fpv_range_lane(K, T, pose_quat(q, i), p[3 * i], p[3 * i + 1], p[3 * i + 2], [&](int r, float t) { out[(int64_t)r * ld + i] = t; });
     return FPV_OK;
 }
 
@@ -1697,16 +1732,10 @@ int depth_constants(const fpv_depth_render_t* s, FpvDepthK* K, FpvObjects* T)
     K->reach = fpv_depth_reach(s->max_depth, s->dir_len_max);
     K->frame_width = s->gate_count > 0 ? s->gate_frame_width : 0.0f;
     K->width = s->width; K->height = s->height; K->gate_count = s->gate_count;
-    if (s->objects && s->objects->count != 0) {
-        if (s->objects->count < 0 || s->objects->count > FPV_MAX_OBJECTS)
-            return fail(FPV_EINVAL, "objects.count out of range (at most " + std::to_string(FPV_MAX_OBJECTS) + " objects)");
-        T->count = s->objects->count;
-        for (int k = 0; k < T->count; ++k) {
-            const fpv_object_t& o = s->objects->obj[k];
-            if (o.type < FPV_OBJ_GROUND || o.type > FPV_OBJ_SPHERE) return fail(FPV_EINVAL, "unknown object type");
-            T->o[k].type = o.type; T->o[k].x = o.x; T->o[k].y = o.y; T->o[k].z = o.z; T->o[k].radius = o.radius; T->o[k].height = o.height;
-        }
-    }
+    int rc = check_object_count(s->objects, true);
+    if (rc == FPV_OK) rc = check_object_types(s->objects);
+    if (rc != FPV_OK) return rc;
+    copy_objects(s->objects, T);
     fpv_range_bounds(*T, K->reach, K->near);
     return FPV_OK;
 }
@@ -1724,17 +1753,11 @@ int depth_image_checks(const fpv_depth_render_t* s)
 
 int fpv_depth_render(fpv_handle_t h, const fpv_buffers_t* b, const fpv_depth_render_t* s, void* stream)
 {
-    if (!fpv_depth_render_kernel_fn)      // (asked first: what a build without the kernel answers to any render)
-        return fail(FPV_EINVAL, "the depth camera is not in this build (the library was linked without csrc/fpv_depth.hip)");
-    if (!h) return fail(FPV_EINVAL, "null handle");
-    if (!b || !s) return fail(FPV_EINVAL, "null argument");
-    if (h->K.flags & FPV_FLAG_FP16_STATE)
-        return fail(FPV_EINVAL, "the depth camera cannot read fp16 state (FPV_FLAG_FP16_STATE): a reader of the packed quaternion is the follow-up");
-    if (!b->state) return fail(FPV_EINVAL, "fpv_buffers_t.state is null");
-    if (b->ld < h->n) return fail(FPV_EALIGN, "fpv_buffers_t.ld is smaller than the number of drones");
+    int rc = check_sensor(h, b, s, fpv_depth_render_kernel_fn != nullptr, "depth camera", "fpv_depth");
+    if (rc != FPV_OK) return rc;
     FpvDepthArgs A;
     memset(&A, 0, sizeof(A));
-    int rc = depth_constants(s, &A.K, &A.T);
+    rc = depth_constants(s, &A.K, &A.T);
     if (rc != FPV_OK) return rc;
     rc = depth_image_checks(s);
     if (rc != FPV_OK) return rc;
@@ -1750,18 +1773,17 @@ int fpv_depth_render(fpv_handle_t h, const fpv_buffers_t* b, const fpv_depth_ren
 
 int fpv_depth_eval(const fpv_depth_render_t* s, int64_t n, const float* p, const float* q)
 {
-    if (!s || !p || !q) return fail(FPV_EINVAL, "null argument");
-    if (n <= 0) return fail(FPV_EINVAL, "n must be positive");
+    int rc = check_eval_args(s, n, p, q);
+    if (rc != FPV_OK) return rc;
     FpvDepthK K;
     FpvObjects T;
-    int rc = depth_constants(s, &K, &T);
+    rc = depth_constants(s, &K, &T);
     if (rc != FPV_OK) return rc;
     rc = depth_image_checks(s);
     if (rc != FPV_OK) return rc;
     const fpv_gate_v4* const gates = reinterpret_cast<const fpv_gate_v4*>(s->gate_descriptors);
     for (int64_t i = 0; i < n; ++i) {
-        FpvQuat a; a.w = q[4 * i]; a.x = q[4 * i + 1]; a.y = q[4 * i + 2]; a.z = q[4 * i + 3];
-        const FpvRot R = fpv_rot(a);
+        const FpvRot R = fpv_rot(pose_quat(q, i));
         float ox, oy, oz;
         fpv_depth_origin(K, R, p[3 * i], p[3 * i + 1], p[3 * i + 2], &ox, &oy, &oz);
         uint32_t obj_mask = 0u;

@@ -2,7 +2,8 @@
 // fpv_range_lane below is what the gfx950 kernel of fpv_range.hip runs for its drone and what fpv_range_eval (fpv_hip.hip, host)
 // runs: the same operations in the same order on the same fp32 values - explicit fmaf, fpv_sqrt_flushed, plain '/', compare-and-
 // select instead of fmaxf / fminf (whose answer for -0 against +0 is the implementation's), no libm call - so the host reproduces
-// the kernel's ranges bit for bit.
+// the kernel's ranges bit for bit.  What a ray does with ONE object is defined here once, for this sensor and for the depth camera
+// (fpv_depth.h fpv_depth_pixel): fpv_range_solid (the interval), fpv_range_nearer (the hit rule), fpv_range_near (the cull's test).
 //
 // Semantics.  A ray set holds 1..FPV_MAX_RAYS directions d_b in the body frame (fpv_rays_derive: unit in double, narrowed once).
 // The ray of a drone starts at o = p and runs along d = R(q) d_b, R = fpv_rot(q) (body -> world); d is NOT renormalised and a range
@@ -128,6 +129,38 @@ FPV_HD FpvInterval fpv_range_round(const FpvRay& y, float ocx, float ocy, float 
     return I;
 }
 
+// THE per-object body of the range scan and of the depth camera: the interval of the ray from o inside the solid `ob`
+FPV_HD FpvInterval fpv_range_solid(const FpvRay& y, float ox, float oy, float oz, const FpvObject& ob)
+{
+    FpvInterval I;
+    if (ob.type == 0) {
+        I = fpv_range_below(y, oz, 0.0f);
+    } else if (ob.type == 1) {
+        I = fpv_range_round<false>(y, ob.x - ox, ob.y - oy, 0.0f, ob.radius);
+        const FpvInterval Z = fpv_range_slab(y, oz, ob.z, ob.z + ob.height);
+        I.t_in = fpv_sel_max(I.t_in, Z.t_in); I.t_out = fpv_sel_min(I.t_out, Z.t_out);
+    } else {
+        I = fpv_range_round<true>(y, ob.x - ox, ob.y - oy, ob.z - oz, ob.radius);
+    }
+    return I;
+}
+
+// ... and THE hit rule: `best`, or the range of a solid that is nearer - `counted`: the lane's own cull flag (see the top)
+FPV_HD float fpv_range_nearer(const FpvInterval& I, bool counted, float best)
+{
+    const bool hit = counted && I.t_in <= I.t_out && I.t_out >= 0.0f;
+    const float t = fpv_sel_max(I.t_in, 0.0f);
+    return (hit && t < best) ? t : best;
+}
+
+// THE near test of the cull: is (x, y, z) within c[3] of the bounding-sphere centre c[0..2] (Ground: below c[3])?  `c` is the
+// object's `near` row (fpv_range_bounds); the range scan asks for the drone's position, the depth camera for its origin.
+FPV_HD bool fpv_range_near(const float* c, int32_t type, float x, float y, float z)
+{
+    const float ux = x - c[0], uy = y - c[1], uz = z - c[2];
+    return type == 0 ? z < c[3] : fmaf(ux, ux, fmaf(uy, uy, uz * uz)) < c[3] * c[3];
+}
+
 // One drone, every ray: `out(r, range)` takes the range of ray r (the kernel stores a row element, the host an array element).
 template <class Out>
 FPV_HD void fpv_range_lane(const FpvRangeK& K, const FpvObjects& T, const FpvQuat& q, float px, float py, float pz, Out&& out)
@@ -136,13 +169,7 @@ FPV_HD void fpv_range_lane(const FpvRangeK& K, const FpvObjects& T, const FpvQua
     // ---- the cull: which objects this lane has to test, and which the wave has (host: the lane is its own wave)
     uint32_t mine = 0u, wave = 0u;
     for (int k = 0; k < T.count; ++k) {
-        const float* c = K.near[k];
-        bool near;
-        if (T.o[k].type == 0) near = pz < c[3];
-        else {
-            const float ux = px - c[0], uy = py - c[1], uz = pz - c[2];
-            near = fmaf(ux, ux, fmaf(uy, uy, uz * uz)) < c[3] * c[3];
-        }
+        const bool near = fpv_range_near(K.near[k], T.o[k].type, px, py, pz);
         mine |= near ? 1u << k : 0u;
         if (FPV_WAVE_ANY(near)) wave |= 1u << k;
     }
@@ -152,20 +179,7 @@ FPV_HD void fpv_range_lane(const FpvRangeK& K, const FpvObjects& T, const FpvQua
         float best = K.max_range;
         for (int k = 0; k < T.count; ++k) {
             if (!((wave >> k) & 1u)) continue;
-            const FpvObject& ob = T.o[k];
-            FpvInterval I;
-            if (ob.type == 0) {
-                I = fpv_range_below(y, pz, 0.0f);
-            } else if (ob.type == 1) {
-                I = fpv_range_round<false>(y, ob.x - px, ob.y - py, 0.0f, ob.radius);
-                const FpvInterval Z = fpv_range_slab(y, pz, ob.z, ob.z + ob.height);
-                I.t_in = fpv_sel_max(I.t_in, Z.t_in); I.t_out = fpv_sel_min(I.t_out, Z.t_out);
-            } else {
-                I = fpv_range_round<true>(y, ob.x - px, ob.y - py, ob.z - pz, ob.radius);
-            }
-            const bool hit = ((mine >> k) & 1u) && I.t_in <= I.t_out && I.t_out >= 0.0f;
-            const float t = fpv_sel_max(I.t_in, 0.0f);
-            best = (hit && t < best) ? t : best;
+            best = fpv_range_nearer(fpv_range_solid(y, px, py, pz, T.o[k]), (mine >> k) & 1u, best);
         }
         out(r, best);
     }

@@ -71,6 +71,7 @@ class _Handle:
         self._ashape = torch.Size((n, 4))
         self._keepalive = self._last_action = self._bcast_action = None
         self._last_action_ptr = 0
+        self._depth_steps = 0           # steps since the last reset() of the env (FpvVecEnv.depth_every)
 
     def _pack(self, params: DroneParams, auto_reset: bool) -> _lib.FpvParams:
         return _lib.pack_params(params, auto_reset=auto_reset, **self._pack_kw)
@@ -199,19 +200,18 @@ class _Handle:
         with torch.cuda.stream(stream):                  # None: the current stream
             return action.to(torch.float32).contiguous()
 
-    def _range_scan_raw(self, scan: "_lib.FpvRangeScan", stream: Optional[torch.cuda.Stream] = None) -> None:
-        """One fpv_range_scan of this handle's drones on `stream` (None: torch's current stream): the state, the step counter and
-        the rotation of the traversal are left alone."""
-        rc = self._L.fpv_range_scan(self._handle, self._buf_ref, C.byref(scan), self._stream() if stream is None else stream.cuda_stream)
+    def _sensor_raw(self, launch: Any, what: C.Structure, stream: Optional[torch.cuda.Stream]) -> None:
+        """One sensor launch (fpv_range_scan, fpv_depth_render) of this handle's drones on `stream` (None: torch's current stream):
+        the state, the step counter and the rotation of the traversal are left alone."""
+        rc = launch(self._handle, self._buf_ref, C.byref(what), self._stream() if stream is None else stream.cuda_stream)
         if rc < 0:
             _lib.check(rc)
 
+    def _range_scan_raw(self, scan: "_lib.FpvRangeScan", stream: Optional[torch.cuda.Stream] = None) -> None:
+        self._sensor_raw(self._L.fpv_range_scan, scan, stream)
+
     def _depth_render_raw(self, render: "_lib.FpvDepthRender", stream: Optional[torch.cuda.Stream] = None) -> None:
-        """One fpv_depth_render of this handle's drones on `stream` (None: torch's current stream): the state, the step counter
-        and the rotation of the traversal are left alone."""
-        rc = self._L.fpv_depth_render(self._handle, self._buf_ref, C.byref(render), self._stream() if stream is None else stream.cuda_stream)
-        if rc < 0:
-            _lib.check(rc)
+        self._sensor_raw(self._L.fpv_depth_render, render, stream)
 
     def _widen(self, cols: int) -> torch.Tensor:
         """fp16 storage decoded into a fresh float32 [14, cols] tensor: one launch of fpv_widen_state on torch's current stream,
@@ -301,7 +301,6 @@ class _Batch(_Handle):
         # the range sensor (fpv_range_scan): `range_rays` [R, 3] unit body-frame directions (fpyv_amd.rays.derive of what was given),
         # `range_rows` [R, ld] the rows a scan writes - an output: checkpoints do not carry them
         self.range_rays = self.range_rows = self._scan = None
-        self._scan_objects = self._scan_object_rows = None
         if range_rays is not None:
             from . import rays as _rays
             self.range_rays = _rays.derive(range_rays)
@@ -311,15 +310,15 @@ class _Batch(_Handle):
         # the depth camera (fpv_depth_render): `depth_camera` a fpyv_amd.camera.DepthCamera, `depth` [num_envs, H, W] float32 or
         # uint8 the images a render writes - caller-visible, zero-copy, an output: checkpoints do not carry them
         self.depth_camera = self.depth = self._render = None
-        self._render_objects = self._render_object_rows = None
         if depth_camera is not None:
             self.depth_camera = depth_camera
             self._render = depth_camera.derive()
             w, h = depth_camera.resolution
             self.depth = torch.zeros((self.n, h, w), dtype=torch.uint8 if depth_camera.encoding == "u8" else torch.float32, device=self.device)
             self._render.image, self._render.image_stride = self.depth.data_ptr(), w * h
-        self._objects = None            # the bound fpv_objects_t (None = no collision world bound)
-        self._object_rows = None
+        self._objects = None            # the address the steps' world is bound at (None = no collision world bound)
+        # the packed tables of the steps' world and of the lists a scan / a render is given (a world that did not move is not re-packed)
+        self._step_table, self._scan_table, self._render_table = _lib.ObjectTable(), _lib.ObjectTable(), _lib.ObjectTable()
         self._override_keep = None
         self._done_bits_keep = None
         self._fill_buffers()
@@ -634,39 +633,26 @@ class _Batch(_Handle):
         self._set_objects(object_list)
 
     def _set_objects(self, object_list) -> None:
-        """Bind the step's object_list (host-side table, read by fpv_step during the call)."""
-        if object_list is None or not len(object_list):
-            if self._buf.objects:
-                self._objects = None
-                self._buf.objects = None
-            return
-        from .objects import to_rows
-        rows = to_rows(object_list)
-        if rows:
-            if rows != self._object_rows or self._objects is None:      # a world that did not move is not re-packed
-                self._objects = _lib.pack_objects(rows)
-                self._object_rows = rows
-            self._buf.objects = C.addressof(self._objects)
-        else:
-            self._objects = None
-            self._buf.objects = None
+        """Bind the step's object_list (host-side table, read by fpv_step during the call); an empty one - or one of things that
+        never collide - clears the binding."""
+        at = None
+        if object_list is not None and len(object_list):
+            at = self._step_table.address(object_list)      # (a bad list raises here: what was bound stays bound)
+            at = at if self._step_table.rows else None
+        self._objects = self._buf.objects = at              # together: `step` reads `_objects` for "nothing is bound"
+
+    def _sensor_world(self, table: "_lib.ObjectTable", object_list) -> Optional[int]:
+        """Where the object list of the next scan or render is: given, it is converted as `step` converts it into the sensor's own
+        `table` (nothing is bound to the steps: a Racer can see a world it does not collide with); None takes what `set_objects`
+        or the last `step` bound, the empty list if nothing is."""
+        return self._buf.objects if object_list is None else table.address(object_list)
 
     # -- range sensor ------------------------------------------------------------------------------
-    def _scan_world(self, object_list) -> None:
-        """The object list of the next scan: given, it is converted as `step` converts it into the scan's own table (nothing is
-        bound to the steps: a Racer can see a world it does not collide with); None takes what `set_objects` or the last `step`
-        bound, the empty list if nothing is."""
+    def _scan_world(self, object_list, scan: Optional["_lib.FpvRangeScan"] = None) -> None:
+        """The object list of the next scan (`_sensor_world`) into `scan`: this batch's, or a partition's copy of it."""
         if self._scan is None:
             raise ValueError("this batch was built without range_rays=")
-        if object_list is None:
-            self._scan.objects = self._buf.objects
-            return
-        from .objects import to_rows
-        rows = to_rows(object_list)
-        if rows != self._scan_object_rows or self._scan_objects is None:      # a world that did not move is not re-packed
-            self._scan_objects = _lib.pack_objects(rows)
-            self._scan_object_rows = rows
-        self._scan.objects = C.addressof(self._scan_objects)
+        (self._scan if scan is None else scan).objects = self._sensor_world(self._scan_table, object_list)
 
     def range_scan(self, object_list=None) -> torch.Tensor:
         """One scan of the range sensor on torch's current stream: for every ray of `range_rays` and every drone, the distance
@@ -683,25 +669,16 @@ class _Batch(_Handle):
         return None if self.range_rows is None else self.range_rows[:, :self.n]
 
     # -- depth camera ------------------------------------------------------------------------------
-    def _render_world(self, object_list) -> None:
-        """The object list and the gates of the next render: a given list is converted as `step` converts it into the render's
-        own table; None takes what `set_objects` or the last `step` bound.  A batch with a bound course passes its own descriptor
-        table: gates that `set_gates` moved are seen where they are."""
+    def _render_world(self, object_list, render: Optional["_lib.FpvDepthRender"] = None) -> None:
+        """The object list (`_sensor_world`) and the gates of the next render into `render`: this batch's, or a partition's copy
+        of it.  A batch with a bound course passes its own descriptor table: gates that `set_gates` moved are seen where they are."""
         if self._render is None:
             raise ValueError("this batch was built without depth_camera=")
-        r = self._render
+        r = self._render if render is None else render
         course = getattr(self, "_course", None)
         r.gate_count = int(course.count) if course is not None else 0
         r.gate_descriptors = self.gate_desc.data_ptr() if course is not None else None
-        if object_list is None:
-            r.objects = self._buf.objects
-            return
-        from .objects import to_rows
-        rows = to_rows(object_list)
-        if rows != self._render_object_rows or self._render_objects is None:  # a world that did not move is not re-packed
-            self._render_objects = _lib.pack_objects(rows)
-            self._render_object_rows = rows
-        r.objects = C.addressof(self._render_objects)
+        r.objects = self._sensor_world(self._render_table, object_list)
 
     def render_depth(self, object_list=None) -> torch.Tensor:
         """One image per drone on torch's current stream: what the drone's `depth_camera` sees of the Ground / Cylinder / Target
@@ -1248,16 +1225,14 @@ class FpvVecEnv:
             kw = dict(position=position, velocity=velocity, ypr=ypr)
         if not self._parts:
             self.batch.reset(mask=mask, **kw)
-            self._range_scan(self.batch)
-            self._depth_after_reset()
+            self._sense_after_reset()
             return self.obs
         cur = self._caller_waits_for_partitions()      # steps still in flight on the partitions' streams finish first
         if self.batch._cparams.flags & _lib.FPV_FLAG_RESET_JITTER:
             # the jitter of an explicit reset is keyed by the step counter: the partitions', which stepped this population
             self.batch.set_step_counter(min(P._steps_launched for P in self._parts))
         self.batch.reset(mask=mask, **kw)              # (the step counters run on, as the unpartitioned batch's does across a reset)
-        self._range_scan(self.batch)
-        self._depth_after_reset()
+        self._sense_after_reset()
         self._partitions_wait_for(cur)
         return self.obs
 
@@ -1286,52 +1261,41 @@ class FpvVecEnv:
         [num_envs, R] block a policy concatenates to `obs`"""
         return self.batch.ranges
 
-    def _range_scan(self, stepper: _Handle, stream: Optional[torch.cuda.Stream] = None) -> None:
-        """The range sensor after a step or a reset of `stepper` (the batch, or a partition on its own stream): the env's
-        collision world, the columns of `stepper`."""
+    def _sense(self, stepper: _Handle, stream: Optional[torch.cuda.Stream] = None, scan: bool = True, render: bool = True) -> None:
+        """The sensors the env was built with after a step or a reset of `stepper` (the batch, or a partition on its own stream):
+        the env's collision world and the batch's course as the batch packs them, the columns of `stepper`."""
         b = self.batch
-        if b.range_rows is None:
-            return
-        b._scan_world(self.object_list)
-        stepper._scan.objects = b._scan.objects
-        stepper._range_scan_raw(stepper._scan, stream)
+        if scan and b.range_rows is not None:
+            b._scan_world(self.object_list, stepper._scan)
+            stepper._range_scan_raw(stepper._scan, stream)
+        if render and b.depth is not None:
+            b._render_world(self.object_list, stepper._render)
+            stepper._depth_render_raw(stepper._render, stream)
 
     @property
     def depth(self) -> Optional[torch.Tensor]:
         """[num_envs, H, W] the depth images after the last render (None without depth_camera=): float32 metres or uint8"""
         return self.batch.depth
 
-    def _depth_render(self, stepper: _Handle, stream: Optional[torch.cuda.Stream] = None) -> None:
-        """The depth camera after a step or a reset of `stepper` (the batch, or a partition on its own stream): the env's
-        collision world and the batch's course, the rows of `stepper`."""
-        b = self.batch
-        if b.depth is None:
-            return
-        b._render_world(self.object_list)
-        r = stepper._render
-        r.objects, r.gate_count, r.gate_descriptors = b._render.objects, b._render.gate_count, b._render.gate_descriptors
-        stepper._depth_render_raw(r, stream)
-
-    def _depth_after_reset(self) -> None:
-        """a reset() is followed by a render of the whole population (unless depth_every = 0) and restarts the count of steps"""
+    def _sense_after_reset(self) -> None:
+        """a reset() is followed by a scan and (unless depth_every = 0) a render of the whole population and restarts the count of steps"""
         for stepper in [self.batch] + self._parts:
             stepper._depth_steps = 0
-        if self.depth_every:
-            self._depth_render(self.batch)
+        self._sense(self.batch, render=bool(self.depth_every))
 
-    def _depth_after_step(self, stepper: _Handle, stream: Optional[torch.cuda.Stream] = None) -> None:
-        """every `depth_every`-th step of `stepper` since the last reset() is followed by a render"""
-        if self.batch.depth is None or self.depth_every == 0:
-            return
-        k = stepper._depth_steps = getattr(stepper, "_depth_steps", 0) + 1
-        if k % self.depth_every == 0:
-            self._depth_render(stepper, stream)
+    def _sense_after_step(self, stepper: _Handle, stream: Optional[torch.cuda.Stream] = None) -> None:
+        """every step of `stepper` is followed by a scan, every `depth_every`-th since the last reset() by a render"""
+        due = False
+        if self.batch.depth is not None and self.depth_every:
+            stepper._depth_steps += 1
+            due = stepper._depth_steps % self.depth_every == 0
+        self._sense(stepper, stream, render=due)
 
     def render_depth(self) -> torch.Tensor:
         """Render every drone's image now, on the caller's stream, ordered after steps in flight like reset; returns `depth`."""
         if self.batch.depth is None:
             raise ValueError("this env was built without depth_camera=")
-        self._whole_population(self._depth_render, self.batch)
+        self._whole_population(self._sense, self.batch, scan=False)
         return self.batch.depth
 
     def _whole_population(self, fn, *a, **kw) -> None:
@@ -1354,8 +1318,7 @@ class FpvVecEnv:
             return self.obs, self.batch.reward, self.batch.done, self._info(self.batch, 0, self.num_envs)
         self._bind_world(self.batch)
         self.batch._step_raw(action)
-        self._range_scan(self.batch)
-        self._depth_after_step(self.batch)
+        self._sense_after_step(self.batch)
         return self.obs, self.batch.reward, self.batch.done, self._info(self.batch, 0, self.num_envs)
 
     def _bind_world(self, stepper: _Handle) -> None:
@@ -1416,8 +1379,7 @@ class FpvVecEnv:
                 P.stream.wait_stream(cur)
         self._bind_world(P)
         P._step_raw(action, stream=P.stream)
-        self._range_scan(P, P.stream)
-        self._depth_after_step(P, P.stream)
+        self._sense_after_step(P, P.stream)
 
     def step_wait(self, part: int, sync: bool = True) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor, Dict[str, Any]]:
         """(obs, reward, done, info) of partition `part` - views of its columns - ordered after its last enqueued step:

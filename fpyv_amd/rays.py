@@ -12,6 +12,7 @@ from typing import Any, Sequence
 import numpy as np
 
 from . import _lib
+from .objects import to_rows
 
 
 def derive(dirs: Any) -> np.ndarray:
@@ -47,15 +48,19 @@ def grid(cols: int, rows: int, hfov_deg: float, vfov_deg: float) -> np.ndarray:
     return derive(np.stack([np.ones(cols * rows), yy.reshape(-1), zz.reshape(-1)], axis=1))
 
 
+def poses(p: Any, q: Any):
+    """The drones a host evaluation (`evaluate`, `DepthCamera.evaluate`) is given, as contiguous float32 p [n, 3] and q [n, 4]"""
+    pp, qq = (np.ascontiguousarray(np.asarray(a, dtype=np.float32).reshape(-1, w)) for a, w in ((p, 3), (q, 4)))
+    if qq.shape[0] != pp.shape[0]:
+        raise ValueError("p and q must describe the same n drones")
+    return pp, qq
+
+
 def evaluate(rays: Any, max_range: float, p: Any, q: Any, object_list: Sequence[Any] = ()) -> np.ndarray:
     """fpv_range_eval: the scan kernel's own lane function on the host, for n drones at once.  `rays` [R, 3] (`derive`), p [n, 3],
     q [n, 4] (wxyz), `object_list` what `step` takes (or raw rows).  Returns the ranges [R, n] float32."""
-    from .objects import to_rows
-    f32 = lambda a, w: np.ascontiguousarray(np.asarray(a, dtype=np.float32).reshape(-1, w))  # noqa: E731
-    pp, qq = f32(p, 3), f32(q, 4)
+    pp, qq = poses(p, q)
     n = pp.shape[0]
-    if qq.shape[0] != n:
-        raise ValueError("p and q must describe the same n drones")
     s = _lib.pack_range_scan(np.asarray(rays, dtype=np.float32).reshape(-1, 3), max_range)
     objs = _lib.pack_objects(to_rows(object_list or ()))
     s.objects = C.addressof(objs)

@@ -11,7 +11,7 @@ import functools
 import numpy as np
 
 from fpyv_amd import gates as GT
-from range_scene import _quadratic, _slab, rot64, table, world  # noqa: F401
+from range_scene import Nearest, rot64, solids, table, world  # noqa: F401
 
 MAX_DEPTH = 25.0
 MARGIN = 1.0e-4             # range_scene's relative margins
@@ -75,40 +75,9 @@ def cast(o, d, object_list=(), gate_rows=None, frame=0.15, max_depth=MAX_DEPTH):
     thing: object index, 100 + gate index, or -1, keep, scale): `keep` is False where a margin of the restatement is too small
     to call (range_scene's, plus a crossing point within EDGE of a frame edge); `scale` is max(depth, distance from the origin to
     the nearest thing's centre) - what an error is measured in."""
-    from fpyv_amd.objects import to_rows
-    rows = np.asarray(to_rows(object_list), dtype=np.float32).astype(np.float64).reshape(-1, 6)
-    shape = d.shape[:-1]
-    oo = o.reshape((o.shape[0],) + (1,) * (d.ndim - 2) + (3,))
-    best, which = np.full(shape, np.inf), np.full(shape, -1)
-    keep, centre = np.ones(shape, bool), np.zeros(shape)
-    pairs = dropped = 0
-
-    def take(t, hit, ok, k, c):
-        nonlocal best, which, centre, keep, pairs, dropped
-        pairs += ok.size
-        dropped += int((~ok).sum())
-        keep &= ok
-        t = np.where(hit, t, np.inf)
-        nearer = t < best
-        best, which = np.where(nearer, t, best), np.where(nearer, k, which)
-        centre = np.where(nearer, np.broadcast_to(np.linalg.norm(c - oo, axis=-1), shape), centre)
-
-    for k, (typ, x, y, z, r, h) in enumerate(rows):
-        c = np.array([x, y, z])
-        margin = np.full(shape, np.inf)
-        if typ == 0:
-            t_in, t_out = _slab(oo[..., 2], d[..., 2], -np.inf, 0.0)
-        elif typ == 1:
-            t_in, t_out, margin = _quadratic((c - oo)[..., :2], d[..., :2], r)
-            z_in, z_out = _slab(oo[..., 2], d[..., 2], z, z + h)
-            t_in, t_out = np.maximum(t_in, z_in), np.minimum(t_out, z_out)
-        else:
-            t_in, t_out, margin = _quadratic(c - oo, d, r)
-        t_in, t_out = np.broadcast_to(t_in, shape), np.broadcast_to(t_out, shape)
-        fin = np.isfinite(t_in) & np.isfinite(t_out)
-        with np.errstate(invalid="ignore"):
-            gap = np.where(fin, np.abs(t_out - t_in) / np.maximum(np.abs(t_in) + np.abs(t_out), 1e-300), np.inf)
-        take(np.maximum(t_in, 0.0), (t_in <= t_out) & (t_out >= 0), (margin >= MARGIN) & (gap >= MARGIN), k, c)
+    near = Nearest(o, d)
+    oo, shape = near.oo, near.shape
+    solids(near, d, object_list)
     if gate_rows is not None:
         for g, row in enumerate(np.asarray(gate_rows, dtype=np.float32).astype(np.float64)):
             c, nrm, u, w = row[0:3], row[3:6], row[6:9], row[9:12]
@@ -129,10 +98,8 @@ def cast(o, d, object_list=(), gate_rows=None, frame=0.15, max_depth=MAX_DEPTH):
                                           np.abs(rho - rout) if np.isfinite(rout) else np.full(shape, np.inf)])
             front = ~par & (t >= 0) & np.isfinite(t)
             ok = ~front | (edge >= EDGE) | (t > 2 * max_depth)
-            take(t, front & outer & ~inner, ok, 100 + g, c)
-    seen = best < max_depth
-    depth = np.where(seen, best, max_depth)
-    return depth, np.where(seen, which, -1), keep, np.maximum(depth, np.where(seen, centre, 0.0)), (pairs, dropped)
+            near.take(t, front & outer & ~inner, ok, 100 + g, c)
+    return near.result(max_depth) + ((near.pairs, near.dropped),)
 
 
 def restate(p, q, cam, object_list=(), gate_rows=None):

@@ -68,37 +68,64 @@ def _slab(o, d, lo, hi):
             np.where(par, np.where(inside, np.inf, -np.inf), np.maximum(t1, t2)))
 
 
-def restate(p, q, rays, object_list, max_range=MAX_RANGE):
-    """float64, from the definition.  Returns (range [R, n], nearest [R, n] object index or -1, keep [R, n] bool, scale [R, n]):
-    `keep` is False where, for some object, the discriminant is below MARGIN of r^2 or the entry / exit gap below MARGIN of
-    |t_in| + |t_out|; `scale` is max(range, distance from the drone to the nearest object's centre) - what an error is measured in."""
+class Nearest:
+    """The nearest thing per ray so far, for origins o [n, 3] and directions d [n, ..., 3] (any shape between), and what the
+    restatements return of it: `take` a thing's t, where it is hit, where its margins are wide enough to call, its index and centre."""
+
+    def __init__(self, o, d):
+        self.shape = d.shape[:-1]
+        self.oo = o.reshape((o.shape[0],) + (1,) * (d.ndim - 2) + (3,))
+        self.best, self.which = np.full(self.shape, np.inf), np.full(self.shape, -1)
+        self.keep, self.centre = np.ones(self.shape, bool), np.zeros(self.shape)
+        self.pairs = self.dropped = 0
+
+    def take(self, t, hit, ok, k, c):
+        self.pairs += ok.size
+        self.dropped += int((~ok).sum())
+        self.keep &= ok
+        t = np.where(hit, t, np.inf)
+        nearer = t < self.best
+        self.best, self.which = np.where(nearer, t, self.best), np.where(nearer, k, self.which)
+        self.centre = np.where(nearer, np.broadcast_to(np.linalg.norm(c - self.oo, axis=-1), self.shape), self.centre)
+
+    def result(self, limit):
+        """(distance, nearest thing or -1, keep, scale): `scale` is max(distance, distance from the origin to the nearest thing's
+        centre) - what an error is measured in"""
+        seen = self.best < limit
+        dist = np.where(seen, self.best, limit)
+        return dist, np.where(seen, self.which, -1), self.keep, np.maximum(dist, np.where(seen, self.centre, 0.0))
+
+
+def solids(near, d, object_list):
+    """THE float64 loop over the solids, from the definition: every object of `object_list` against the rays of `near` (a Nearest)
+    along d.  A ray is not kept where, for some object, the discriminant is below MARGIN of r^2 or the entry / exit gap below
+    MARGIN of |t_in| + |t_out|."""
     from fpyv_amd.objects import to_rows
     rows = np.asarray(to_rows(object_list), dtype=np.float32).astype(np.float64).reshape(-1, 6)
-    o = p.astype(np.float64)
-    d = np.einsum("nij,rj->rni", rot64(q), rays.astype(np.float64))                 # [R, n, 3]
-    R, n = d.shape[0], d.shape[1]
-    best, which = np.full((R, n), np.inf), np.full((R, n), -1)
-    keep, centre = np.ones((R, n), bool), np.zeros((R, n))
+    oo, shape = near.oo, near.shape
     for k, (typ, x, y, z, r, h) in enumerate(rows):
         c = np.array([x, y, z])
-        margin = np.full((R, n), np.inf)
+        margin = np.full(shape, np.inf)
         if typ == 0:
-            t_in, t_out = _slab(o[None, :, 2], d[..., 2], -np.inf, 0.0)
+            t_in, t_out = _slab(oo[..., 2], d[..., 2], -np.inf, 0.0)
         elif typ == 1:
-            t_in, t_out, margin = _quadratic((c - o)[None, :, :2], d[..., :2], r)
-            z_in, z_out = _slab(o[None, :, 2], d[..., 2], z, z + h)
+            t_in, t_out, margin = _quadratic((c - oo)[..., :2], d[..., :2], r)
+            z_in, z_out = _slab(oo[..., 2], d[..., 2], z, z + h)
             t_in, t_out = np.maximum(t_in, z_in), np.minimum(t_out, z_out)
         else:
-            t_in, t_out, margin = _quadratic((c - o)[None], d, r)
+            t_in, t_out, margin = _quadratic(c - oo, d, r)
+        t_in, t_out = np.broadcast_to(t_in, shape), np.broadcast_to(t_out, shape)
         fin = np.isfinite(t_in) & np.isfinite(t_out)
         with np.errstate(invalid="ignore"):
             gap = np.where(fin, np.abs(t_out - t_in) / np.maximum(np.abs(t_in) + np.abs(t_out), 1e-300), np.inf)
-        keep &= (margin >= MARGIN) & (gap >= MARGIN)
-        hit = (t_in <= t_out) & (t_out >= 0)
-        t = np.where(hit, np.maximum(t_in, 0.0), np.inf)
-        nearer = t < best
-        best, which = np.where(nearer, t, best), np.where(nearer, k, which)
-        centre = np.where(nearer, np.linalg.norm(c - o, axis=1)[None], centre)
-    seen = best < max_range
-    rng = np.where(seen, best, max_range)
-    return rng, np.where(seen, which, -1), keep, np.maximum(rng, np.where(seen, centre, 0.0))
+        near.take(np.maximum(t_in, 0.0), (t_in <= t_out) & (t_out >= 0), (margin >= MARGIN) & (gap >= MARGIN), k, c)
+
+
+def restate(p, q, rays, object_list, max_range=MAX_RANGE):
+    """float64, from the definition.  Returns (range [R, n], nearest [R, n] object index or -1, keep [R, n] bool, scale [R, n]):
+    `keep` is False where a margin of `solids` is too small to call; `scale` is max(range, distance from the drone to the nearest
+    object's centre) - what an error is measured in."""
+    d = np.einsum("nij,rj->rni", rot64(q), rays.astype(np.float64)).transpose(1, 0, 2)      # [n, R, 3]
+    near = Nearest(p.astype(np.float64), d)
+    solids(near, d, object_list)
+    return tuple(np.ascontiguousarray(a.T) for a in near.result(max_range))
