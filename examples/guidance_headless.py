@@ -6,14 +6,17 @@ drones at once, headless:
     drone.step(action=action, wind_velocity_vector=wind, object_list=object_list,
                rotation_matrix=rot_mat, thrust_force=force_size)                      # components.py:230-232
 
-The reference derives (rot_mat, force_size) from the camera image of the target
-(Drone.calculate_needed_force_orientation, out of scope: rendering); here a plain geometric law stands in for it -
-point the body z axis along "gravity compensation + a pull towards the target", thrust = that vector's length - so
-that the example exercises the same call with the same argument shapes: rotation_matrix [N,3,3], thrust_force [N].
-Drones further than --engage metres from the target are left to their sticks (NaN thrust_force = not overridden),
-like the released gamepad button of simulator.py:104.
+--law geometric (the default): a plain geometric law stands in for it - point the body z axis along "gravity compensation + a
+pull towards the target", thrust = that vector's length - written in torch, so that the example exercises the call with
+the argument shapes rotation_matrix [N,3,3], thrust_force [N].  Drones further than --engage metres from the target are
+left to their sticks (NaN thrust_force = not overridden), like the released gamepad button of simulator.py:104.
 
-Usage:  python examples/guidance_headless.py --drones 65536 --steps 3000
+--law reference: the reference's own law, Drone.calculate_needed_force_orientation(pixel, target) (components.py:258-304), in
+one kernel per step: target.update(), calculate_needed_force_orientation(None, target) - None: the pixel is where the drone's
+camera sees the target -, step(..., rotation_matrix=, thrust_force=).  Drones that do not see the target are left to their
+sticks (simulator.py:104-105).
+
+Usage:  python examples/guidance_headless.py --drones 65536 --steps 3000 [--law reference]
 """
 import argparse
 import os
@@ -46,6 +49,7 @@ def main():
     ap.add_argument("--engage", type=float, default=60.0, help="guidance takes over within this distance of the target [m]")
     ap.add_argument("--gain", type=float, default=1.5, help="pull towards the target [1/s^2]")
     ap.add_argument("--damp", type=float, default=2.0, help="velocity damping [1/s]")
+    ap.add_argument("--law", choices=("geometric", "reference"), default="geometric")
     a = ap.parse_args()
     dev = "cuda:0"
     rng = np.random.default_rng(0)
@@ -53,8 +57,12 @@ def main():
     target = Target(np.array([0.0, 0.0, 12.0]), 1.0, 5, {"radius": 25.0, "resolution": 20000})
     ground = Ground(size=60, resolution=50, random=False)
     drone = Drone(params, num_envs=a.drones, device=dev)
-    drone.reset(position=rng.uniform([-40, -40, 5], [40, 40, 30], (a.drones, 3)).astype(np.float32),
-                velocity=np.zeros(3), ypr=np.zeros(3))
+    start = rng.uniform([-40, -40, 5], [40, 40, 30], (a.drones, 3)).astype(np.float32)
+    if a.law == "reference":
+        # the law guides a drone whose camera sees the target within its 15 m reach: start behind the first point of the target's
+        # path, (25, 0, 12), nose towards it (the camera looks 35 degrees up)
+        start = rng.uniform([13, -6, 7], [21, 6, 12], (a.drones, 3)).astype(np.float32)
+    drone.reset(position=start, velocity=np.zeros(3), ypr=np.zeros(3))
     sticks = torch.tensor([0.0, 0.0, 0.0, -0.646], device=dev).expand(a.drones, 4).contiguous()   # hover throttle when not engaged
     g = torch.tensor([0.0, 0.0, params.gravity], device=dev)
     heading = torch.tensor([1.0, 0.0, 0.0], device=dev).expand(a.drones, 3)
@@ -68,17 +76,21 @@ def main():
         tpos = torch.as_tensor(np.asarray(target.position, dtype=np.float32), device=dev)
         to_target = tpos - drone.position
         dist = to_target.norm(dim=1)
-        closest = torch.minimum(closest, dist)
-        want = g + a.gain * to_target - a.damp * drone.velocity             # acceleration the thrust has to supply
-        rot_mat = look_along(want, heading)
-        force_size = params.mass * want.norm(dim=1)
-        force_size = torch.where(dist < a.engage, force_size, torch.full_like(force_size, float("nan")))
+        closest = torch.minimum(closest, dist)                              # bookkeeping of the example, the same for both laws
+        if a.law == "reference":
+            rot_mat, force_size = drone.calculate_needed_force_orientation(None, target)        # simulator.py:109
+        else:
+            want = g + a.gain * to_target - a.damp * drone.velocity         # acceleration the thrust has to supply
+            rot_mat = look_along(want, heading)
+            force_size = params.mass * want.norm(dim=1)
+            force_size = torch.where(dist < a.engage, force_size, torch.full_like(force_size, float("nan")))
         drone.step(action=sticks, wind_velocity_vector=wind, object_list=[target, ground],
-                   rotation_matrix=rot_mat, thrust_force=force_size, return_imu=False)
+                   rotation_matrix=rot_mat, thrust_force=force_size, return_imu=False)           # simulator.py:110
     torch.cuda.synchronize()
     dt = time.perf_counter() - t0
     print(f"{a.drones} drones x {a.steps} guided steps (dt = {params.dt * 1e3:.1f} ms) in {dt:.3f} s = "
-          f"{a.drones * a.steps / dt / 1e6:.1f} M env-steps/s (host loop: torch guidance law + one fused step per step)")
+          f"{a.drones * a.steps / dt / 1e6:.1f} M env-steps/s "
+          + ("(host loop: torch guidance law + one fused step per step)" if a.law == "geometric" else "(host loop: one guidance kernel + one fused step per step)"))
     print(f"closest approach to the moving target: median {float(closest.median()):.2f} m, "
           f"within 3 m: {int((closest < 3.0).sum())} of {a.drones}; finite state: {bool(torch.isfinite(drone.position).all())}")
 

@@ -34,6 +34,9 @@ GATE_OBS_ROWS = 6
 FPV_MAX_RAYS = 32             # fpv_range_scan: a ray set has 1..32 body-frame directions (fpv_abi.h "Range scan")
 FPV_DEPTH_MAX_SIDE = 128      # fpv_depth_render: an image is 4..128 pixels wide and high (fpv_abi.h "Depth camera")
 DEPTH_ENCODINGS = {"metres": 0, "u8": 1}
+FPV_CHASE_MAX_SIDE = 16384    # fpv_chase_guide: no image is written, the camera may be 1..16384 pixels wide and high ("Target chase")
+CHASE_FRAMES = {"world": 0, "drone": 1}
+CHASE_MODES = {"level": 0, "frontarget": 1}
 FPV_HALF_PAIR_ROWS = 5
 FPV_HALF_HALVES = 11          # binary16 values per drone in state_h (5 pair rows + 1 half row)
 FPV_OBS_AOS_DIM = 16
@@ -52,7 +55,8 @@ EXPORTS = ("fpv_abi_version", "fpv_sizeof", "fpv_state_rows", "fpv_algorithmic_b
            "fpv_physics_rows", "fpv_physics_derive", "fpv_physics_sample", "fpv_set_physics", "fpv_get_physics",
            "fpv_gates_derive", "fpv_set_gates", "fpv_gate_eval",
            "fpv_rays_derive", "fpv_range_scan", "fpv_range_eval",
-           "fpv_camera_derive", "fpv_depth_render", "fpv_depth_eval")
+           "fpv_camera_derive", "fpv_depth_render", "fpv_depth_eval",
+           "fpv_chase_derive", "fpv_chase_guide", "fpv_chase_eval")
 
 
 class FpvParams(C.Structure):
@@ -263,6 +267,18 @@ class FpvDepthRender(C.Structure):
                 ("objects", C.c_void_p), ("gate_descriptors", C.c_void_p)]
 
 
+class FpvChase(C.Structure):
+    """fpv_chase_t: the camera numbers fpv_chase_derive wrote, the law's constants, frame and mode, the target, the guidance PID's
+    constants and rows, the optional pixels and the outputs (device for fpv_chase_guide, host for fpv_chase_eval)."""
+    _fields_ = [("struct_size", C.c_uint32), ("width", C.c_int32), ("height", C.c_int32), ("ref_frame", C.c_int32), ("mode", C.c_int32),
+                ("_reserved", C.c_int32), ("focal_length", C.c_double), ("relative_rotation", C.c_double * 9),
+                ("relative_position", C.c_double * 3), ("max_depth", C.c_double), ("mass", C.c_double),
+                ("virtual_drag_coefficient", C.c_double), ("virtual_lift_coefficient", C.c_double), ("tof_effective_distance", C.c_double),
+                ("keep_distance", C.c_double), ("UWB_sensor_max_range", C.c_double), ("target", C.c_float * 3), ("target_radius", C.c_float),
+                ("pid", FpvPidParams), ("pid_state", C.c_void_p), ("pid_ld", C.c_int64), ("pixel", C.c_void_p), ("rotation", C.c_void_p),
+                ("thrust", C.c_void_p), ("pixel_out", C.c_void_p), ("visible", C.c_void_p)]
+
+
 class FpvCacheModel(C.Structure):
     """fpv_cache_model_t: what a device says about itself, held against the cache model of the rotation / row stride."""
     _fields_ = [("struct_size", C.c_uint32), ("matches", C.c_int32), ("compute_units", C.c_int32), ("xcds", C.c_int32),
@@ -356,11 +372,14 @@ def lib() -> C.CDLL:
     L.fpv_camera_derive.argtypes = [C.POINTER(FpvCamera), C.POINTER(FpvDepthRender)]
     L.fpv_depth_render.argtypes = [vp, pb, C.POINTER(FpvDepthRender), vp]
     L.fpv_depth_eval.argtypes = [C.POINTER(FpvDepthRender), i64, vp, vp]
+    L.fpv_chase_derive.argtypes = [C.POINTER(FpvCamera), C.POINTER(FpvChase)]
+    L.fpv_chase_guide.argtypes = [vp, pb, C.POINTER(FpvChase), vp]
+    L.fpv_chase_eval.argtypes = [C.POINTER(FpvChase), i64, vp, vp, vp]
     if L.fpv_abi_version() != FPV_ABI_VERSION:
         raise ImportError(f"libfpv_hip.so ABI {L.fpv_abi_version()} != binding {FPV_ABI_VERSION} - rebuild the library "
                           "(`python -c 'import __graft_entry__ as g; g.build()'`)")
     for which, struct in ((0, FpvParams), (1, FpvBuffers), (2, FpvObjects), (3, FpvPidParams), (4, FpvCacheModel), (5, FpvGateCourse),
-                          (6, FpvRangeScan), (7, FpvDepthRender)):
+                          (6, FpvRangeScan), (7, FpvDepthRender), (8, FpvChase)):
         if L.fpv_sizeof(which) != C.sizeof(struct):
             raise ImportError(f"{struct.__name__}: ctypes declares {C.sizeof(struct)} bytes, libfpv_hip.so has "
                               f"{L.fpv_sizeof(which)} - _lib.py and include/fpv_abi.h are out of step")

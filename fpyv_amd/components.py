@@ -2,15 +2,16 @@
 the per-drone step: `from fpyv_amd.components import Drone, Ground, Cylinder, Target, Gate, Trail, PID`.
 
     reference class (src/utils/components.py)      here
-    Drone   :72-248                                 fpyv_amd.env.DroneBatch  (N drones per object; `Drone(params)`
-                                                    takes the same params dict, plus num_envs= / device=)
+    Drone   :72-248, :258-304                       fpyv_amd.env.DroneBatch  (N drones per object; `Drone(params)`
+                                                    takes the same params dict, plus num_envs= / device=;
+                                                    calculate_needed_force_orientation is DESIGN 3.9)
     PID     :15-54                                  fpyv_amd.pid.PID         (N controllers per object)
     Ground  :646-683, Cylinder :685-729,            fpyv_amd.objects         (reference constructor signatures;
     Target  :753-778, Gate :780-831, Trail :631-644                           distance + normal only, Gate/Trail inert)
 
 `Racer` (/root/reference/tests/racer_drone_test.py:68-103) maps to fpyv_amd.env.RacerBatch.
 `Camera` (:449-629) maps to fpyv_amd.camera.Camera: the reference's constructor signature on the batched depth camera (DESIGN 3.8;
-its rendering of point clouds and the guidance methods are out of scope).
+its rendering of point clouds is out of scope).
 """
 from .camera import Camera  # noqa: F401
 from .env import DroneBatch as Drone, RacerBatch as Racer, FpvVecEnv  # noqa: F401

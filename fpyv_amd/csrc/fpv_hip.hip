@@ -37,6 +37,7 @@
 #include "fpv_kernels.h"
 #include "fpv_range.h"
 #include "fpv_depth.h"
+#include "fpv_chase.h"
 
 namespace {
 
@@ -861,6 +862,10 @@ extern "C" __attribute__((weak, visibility("hidden"))) void* fpv_range_scan_kern
 // The kernels of csrc/fpv_depth.hip (one per encoding), weak in the same way (fpv_depth_render says so when they are absent): one
 // FpvDepthArgs.
 extern "C" __attribute__((weak, visibility("hidden"))) void* fpv_depth_render_kernel_fn(int u8);
+// The kernels of csrc/fpv_chase.hip (with and without a supplied pixel) and its host loop, weak in the same way (fpv_chase_guide and
+// fpv_chase_eval say so when they are absent): one FpvChaseArgs.
+extern "C" __attribute__((weak, visibility("hidden"))) void* fpv_chase_kernel_fn(int pixel);
+extern "C" __attribute__((weak, visibility("hidden"))) void fpv_chase_eval_host(const FpvChaseArgs* A, const float* p, const float* v, const float* q);
 
 namespace {
 
@@ -1425,7 +1430,8 @@ int fpv_sizeof(int which)
         case 5: return (int)sizeof(fpv_gate_course_t);
         case 6: return (int)sizeof(fpv_range_scan_t);
         case 7: return (int)sizeof(fpv_depth_render_t);
-        default: return fail(FPV_EINVAL, "fpv_sizeof: 0 = fpv_params_t, 1 = fpv_buffers_t, 2 = fpv_objects_t, 3 = fpv_pid_params_t, 4 = fpv_cache_model_t, 5 = fpv_gate_course_t, 6 = fpv_range_scan_t, 7 = fpv_depth_render_t");
+        case 8: return (int)sizeof(fpv_chase_t);
+        default: return fail(FPV_EINVAL, "fpv_sizeof: 0 = fpv_params_t, 1 = fpv_buffers_t, 2 = fpv_objects_t, 3 = fpv_pid_params_t, 4 = fpv_cache_model_t, 5 = fpv_gate_course_t, 6 = fpv_range_scan_t, 7 = fpv_depth_render_t, 8 = fpv_chase_t");
     }
 }
 
@@ -1799,6 +1805,107 @@ int fpv_depth_eval(const fpv_depth_render_t* s, int64_t n, const float* p, const
                 else static_cast<float*>(s->image)[at] = d;
             }
     }
+    return FPV_OK;
+}
+
+int fpv_chase_derive(const fpv_camera_t* camera, fpv_chase_t* out)
+{
+    if (!camera || !out) return fail(FPV_EINVAL, "null argument");
+    const char* why = "";
+    const int rc = fpv_chase_derive_camera(*camera, out, &why);
+    return rc == FPV_OK ? FPV_OK : fail(rc, std::string("camera: ") + why);
+}
+
+namespace {
+
+const char kChaseAbsent[] = "the target chase is not in this build (the library was linked without csrc/fpv_chase.hip)";
+
+// the uniform constants of a call and its buffers, checked (n: the drones the buffers must hold): FPV_OK or the error
+int chase_args(const fpv_chase_t* s, int64_t n, FpvChaseArgs* A)
+{
+    if (s->struct_size != sizeof(fpv_chase_t)) return fail(FPV_EINVAL, "fpv_chase_t.struct_size does not match this library");
+    if (s->width < 1 || s->width > FPV_CHASE_MAX_SIDE || s->height < 1 || s->height > FPV_CHASE_MAX_SIDE)
+        return fail(FPV_EINVAL, "width and height must be 1.." + std::to_string(FPV_CHASE_MAX_SIDE) + " pixels, not " + std::to_string(s->width) + " x " + std::to_string(s->height));
+    if (s->ref_frame != FPV_CHASE_WORLD && s->ref_frame != FPV_CHASE_DRONE) return fail(FPV_EINVAL, "unknown ref_frame (0 FPV_CHASE_WORLD, 1 FPV_CHASE_DRONE)");
+    if (s->mode != FPV_CHASE_LEVEL && s->mode != FPV_CHASE_FRONTARGET) return fail(FPV_EINVAL, "unknown mode (0 FPV_CHASE_LEVEL, 1 FPV_CHASE_FRONTARGET)");
+    if (!isfinite(s->focal_length) || !(s->focal_length > 0.0)) return fail(FPV_EINVAL, "focal_length must be finite and positive (it comes from fpv_chase_derive)");
+    for (int k = 0; k < 9; ++k)
+        if (!isfinite(s->relative_rotation[k]) || !isfinite(s->relative_position[k % 3]))
+            return fail(FPV_EINVAL, "relative_rotation and relative_position must be finite (they come from fpv_chase_derive)");
+    if (!isfinite(s->max_depth) || !(s->max_depth > 0.0)) return fail(FPV_EINVAL, "max_depth must be finite and positive");
+    if (!isfinite(s->mass) || !(s->mass > 0.0)) return fail(FPV_EPARAM, "mass must be finite and positive");
+    const double five[5] = {s->virtual_drag_coefficient, s->virtual_lift_coefficient, s->tof_effective_distance, s->keep_distance, s->UWB_sensor_max_range};
+    const char* const names[5] = {"virtual_drag_coefficient", "virtual_lift_coefficient", "tof_effective_distance", "keep_distance", "UWB_sensor_max_range"};
+    for (int k = 0; k < 5; ++k)
+        if (!isfinite(five[k])) return fail(FPV_EPARAM, std::string(names[k]) + " is not finite");
+    for (int k = 0; k < 3; ++k)
+        if (!isfinite(s->target[k])) return fail(FPV_EPARAM, "the target's centre is not finite");
+    if (!isfinite(s->target_radius) || !(s->target_radius >= 0.0f)) return fail(FPV_EPARAM, "the target's radius must be finite and not negative");
+    const fpv_pid_params_t& P = s->pid;
+    if (P.struct_size != sizeof(fpv_pid_params_t)) return fail(FPV_EINVAL, "fpv_chase_t.pid.struct_size does not match this library");
+    const double pid[8] = {P.kP, P.kI, P.kD, P.dt, P.integral_clip, P.min_output, P.max_output, P.derivative_transition_rate};
+    for (int k = 0; k < 8; ++k)
+        if (!isfinite(pid[k])) return fail(FPV_EPARAM, "a PID constant is not finite");
+    if (!(P.dt > 0)) return fail(FPV_EPARAM, "dt must be positive");
+    if (!(P.integral_clip >= 0) || !(P.min_output <= P.max_output) || !(P.derivative_transition_rate >= 0 && P.derivative_transition_rate <= 1))
+        return fail(FPV_EPARAM, "components.PID constants: integral_clip >= 0, min_output <= max_output, derivative_transition_rate in [0, 1]");
+    if (!s->pid_state) return fail(FPV_EINVAL, "fpv_chase_t.pid_state is null");
+    if (!s->rotation) return fail(FPV_EINVAL, "fpv_chase_t.rotation is null");
+    if (!s->thrust) return fail(FPV_EINVAL, "fpv_chase_t.thrust is null");
+    if (s->pid_ld < n) return fail(FPV_EALIGN, "fpv_chase_t.pid_ld is smaller than the number of drones");
+    if (((uintptr_t)s->pid_state & 3) || ((uintptr_t)s->rotation & 3) || ((uintptr_t)s->thrust & 3))
+        return fail(FPV_EALIGN, "pid_state, rotation and thrust must be 4-byte aligned");
+    if (((uintptr_t)s->pixel & 7) || ((uintptr_t)s->pixel_out & 7)) return fail(FPV_EALIGN, "pixel and pixel_out must be 8-byte aligned");
+    memset(A, 0, sizeof(*A));
+    FpvChaseK& K = A->K;
+    for (int k = 0; k < 9; ++k) K.rr[k] = (float)s->relative_rotation[k];
+    for (int k = 0; k < 3; ++k) { K.rel[k] = (float)s->relative_position[k]; K.tc[k] = s->target[k]; }
+    K.f = (float)s->focal_length; K.cx = (float)(0.5 * s->width); K.cy = (float)(0.5 * s->height); K.w = (float)s->width; K.h = (float)s->height;
+    K.max_depth = (float)s->max_depth; K.tr = s->target_radius;
+    K.gz = (float)(-9.81 * s->mass);                                     // kinematics.gravity_vector(mass, g=9.81): components.py:270
+    K.vdrag = (float)five[0]; K.vlift = (float)five[1]; K.tof = (float)five[2]; K.keep = (float)five[3]; K.uwb = (float)five[4];
+    K.frame = s->ref_frame; K.mode = s->mode;
+    K.pid.dt = (float)P.dt; K.pid.inv_dt = (float)(1.0 / P.dt);
+    K.pid.gain[0][0] = (float)P.kP; K.pid.gain[0][1] = (float)P.kI; K.pid.gain[0][2] = (float)P.kD;
+    K.pid.integral_clip = (float)P.integral_clip; K.pid.min_output = (float)P.min_output; K.pid.max_output = (float)P.max_output;
+    K.pid.d_rate = (float)P.derivative_transition_rate; K.pid.om_d_rate = (float)(1.0 - P.derivative_transition_rate);
+    A->pid_state = s->pid_state; A->pid_ld = s->pid_ld; A->pixel = s->pixel; A->rotation = s->rotation; A->thrust = s->thrust;
+    A->pixel_out = s->pixel_out; A->visible = s->visible; A->n = n;
+    return FPV_OK;
+}
+
+}  // namespace
+
+int fpv_chase_guide(fpv_handle_t h, const fpv_buffers_t* b, const fpv_chase_t* s, void* stream)
+{
+    if (fpv_chase_kernel_fn == nullptr) return fail(FPV_EINVAL, kChaseAbsent);
+    if (!h) return fail(FPV_EINVAL, "null handle");
+    if (!b || !s) return fail(FPV_EINVAL, "null argument");
+    if (h->mode != FPV_MODE_DRONE) return fail(FPV_EINVAL, "the target chase is the Drone's guidance law: not for a Racer handle");
+    if (h->K.flags & FPV_FLAG_FP16_STATE)
+        return fail(FPV_EINVAL, "the target chase cannot read fp16 state (FPV_FLAG_FP16_STATE): a reader of the packed quaternion is the follow-up");
+    if (!b->state) return fail(FPV_EINVAL, "fpv_buffers_t.state is null");
+    if (b->ld < h->n) return fail(FPV_EALIGN, "fpv_buffers_t.ld is smaller than the number of drones");
+    FpvChaseArgs A;
+    const int rc = chase_args(s, h->n, &A);
+    if (rc != FPV_OK) return rc;
+    A.state = b->state; A.ld = b->ld;
+    const DeviceGuard dev(h->device);
+    if (dev.rc != FPV_OK) return dev.rc;
+    void* arg = &A;
+    return launch_args("chase kernel launch", fpv_chase_kernel_fn(s->pixel != nullptr), blocks_for(h->n, kStepBlock), dim3(kStepBlock), (hipStream_t)stream, &arg);
+}
+
+int fpv_chase_eval(const fpv_chase_t* s, int64_t n, const float* p, const float* v, const float* q)
+{
+    if (fpv_chase_eval_host == nullptr) return fail(FPV_EINVAL, kChaseAbsent);
+    if (!v) return fail(FPV_EINVAL, "null argument");
+    int rc = check_eval_args(s, n, p, q);
+    if (rc != FPV_OK) return rc;
+    FpvChaseArgs A;
+    rc = chase_args(s, n, &A);
+    if (rc != FPV_OK) return rc;
+    fpv_chase_eval_host(&A, p, v, q);
     return FPV_OK;
 }
 

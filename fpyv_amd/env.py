@@ -690,6 +690,80 @@ class _Batch(_Handle):
         self._depth_render_raw(self._render)
         return self.depth
 
+    # -- target chase ------------------------------------------------------------------------------
+    def _chase_rows(self) -> torch.Tensor:
+        """The [4, ld] guidance-PID rows the law reads and advances: `force_multiplier_pid`'s own state where the batch has one"""
+        pid = getattr(self, "force_multiplier_pid", None)
+        if pid is not None:
+            return pid.state
+        if getattr(self, "_chase_scratch_rows", None) is None:
+            self._chase_scratch_rows = torch.zeros((_lib.FPV_PID_ROWS, self.ld), dtype=torch.float32, device=self.device)
+        return self._chase_scratch_rows
+
+    def set_chase_camera(self, camera=None, max_depth: float = 15.0) -> None:
+        """The camera the target chase looks through - a fpyv_amd.camera.DepthCamera / Camera; None: the params' `camera` section,
+        the reference's 640 x 480 - and the reach within which it sees the target (simulator.py:102: 15).  Takes effect with the
+        next `calculate_needed_force_orientation` / `track`."""
+        self._chase_camera, self._chase_structs = (camera, float(max_depth)), {}
+
+    def _chase(self, pixel, target, ref_frame: str, mode: str, rows: torch.Tensor):
+        """One launch of fpv_chase_guide on torch's current stream into the preallocated outputs"""
+        from .chase import ChaseGuidance, target_row
+        if getattr(self, "_chase_camera", None) is None:
+            self.set_chase_camera()
+        if getattr(self, "_chase_out", None) is None:
+            f32 = dict(dtype=torch.float32, device=self.device)
+            self._chase_out = (torch.zeros((self.n, 3, 3), **f32), torch.zeros(self.n, **f32), torch.zeros((self.n, 2), **f32),
+                               torch.zeros(self.n, dtype=torch.bool, device=self.device))
+        key = (ref_frame, mode)
+        if key not in self._chase_structs:
+            camera, max_depth = self._chase_camera
+            self._chase_structs[key] = ChaseGuidance(self.params, camera=camera, ref_frame=ref_frame, mode=mode, max_depth=max_depth).derive()
+        s = self._chase_structs[key]
+        c, r = target_row(target)
+        s.target[:] = [float(x) for x in c]
+        s.target_radius = r
+        rot, thrust, pix, vis = self._chase_out
+        if rows is not self._chase_rows():            # `track`: the law's outputs of a scratch PID go to scratch tensors
+            if getattr(self, "_chase_track_out", None) is None:
+                self._chase_track_out = (torch.zeros_like(rot), torch.zeros_like(thrust))
+            rot, thrust = self._chase_track_out
+        keep = None
+        if pixel is not None:
+            keep = torch.as_tensor(np.asarray(pixel, dtype=np.float32) if not torch.is_tensor(pixel) else pixel,
+                                   dtype=torch.float32, device=self.device)
+            if keep.shape == (2,):
+                keep = keep.expand(self.n, 2)
+            if keep.shape != (self.n, 2):
+                raise ValueError(f"pixel must be [2] or [{self.n}, 2] in (x, y) order, got {tuple(keep.shape)}")
+            keep = keep.contiguous()
+        s.pixel = keep.data_ptr() if keep is not None else None
+        s.pid_state, s.pid_ld = rows.data_ptr(), rows.shape[1]
+        s.rotation, s.thrust, s.pixel_out, s.visible = rot.data_ptr(), thrust.data_ptr(), pix.data_ptr(), vis.data_ptr()
+        self._sensor_raw(self._L.fpv_chase_guide, s, None)
+        self._chase_keep = keep
+        return rot, thrust, pix, vis
+
+    def calculate_needed_force_orientation(self, pixel, target, ref_frame: str = "world", mode: str = "level"):
+        """Drone.calculate_needed_force_orientation (components.py:258-304) for every drone, one kernel: `pixel` [num_envs, 2]
+        (x, y) where the drone's camera sees `target`, or None = find it (the projection of the target's centre; include/fpv_abi.h
+        "Target chase").  Returns (rotation_matrix [num_envs, 3, 3], thrust_force [num_envs]) in preallocated tensors that the
+        next call overwrites - what `step(..., rotation_matrix=, thrust_force=)` takes as they are.  A drone that does not see the
+        target gets thrust_force NaN (step: not overridden) and an identity matrix.  Uses and advances `force_multiplier_pid`'s
+        state for the drones it guides; `reset(mask)` clears it."""
+        rot, thrust, _, _ = self._chase(pixel, target, ref_frame, mode, self._chase_rows())
+        return rot, thrust
+
+    def track(self, target):
+        """(pixel [num_envs, 2] in (x, y) order, visible [num_envs] bool): where every drone's camera sees the centre of `target`
+        (NaN where it does not) - the pixel alone: no PID is advanced and the outputs of the last
+        `calculate_needed_force_orientation` stay as they are.  It is the same kernel run on scratch PID rows and scratch
+        matrices: a launch of the whole law for its first step, not a kernel of its own."""
+        if getattr(self, "_chase_track_rows", None) is None:
+            self._chase_track_rows = torch.zeros((_lib.FPV_PID_ROWS, self.ld), dtype=torch.float32, device=self.device)
+        _, _, pix, vis = self._chase(None, target, "world", "level", self._chase_track_rows)
+        return pix, vis
+
     def set_done_bits_target(self, target: Any = None, stride_words: int = 0) -> None:
         """Where the kernel writes the bit-packed done mask (one wave ballot per 64 drones):
         an int64 tensor of at least ceil(num_envs / 64) words or a raw device address; None restores the

@@ -143,6 +143,14 @@ class DroneParams:
     # min_output / max_output are replaced by the 5 % / full throttle forces when the drone builds the controller
     force_multiplier_pid: Dict[str, float] = dataclasses.field(default_factory=lambda: dict(
         kP=0.1, kI=2.0, kD=0.05, integral_clip=100.0, min_output=0.05, max_output=40.0, derivative_transition_rate=0.2))
+    # the guidance law Drone.calculate_needed_force_orientation (components.py:114-118, :258-304): drone.keep_distance,
+    # drone.UWB_sensor_max_range and the point_and_shoot section of params.yaml (:53-54, :71-76), and its camera section (:64-68)
+    keep_distance: float = 6.0
+    UWB_sensor_max_range: float = 13.0
+    point_and_shoot: Dict[str, Any] = dataclasses.field(default_factory=lambda: dict(
+        ref_frame="world", mode="level", virtual_drag_coefficient=0.5, virtual_lift_coefficient=0.1, tof_effective_distance=2.0))
+    camera: Dict[str, Any] = dataclasses.field(default_factory=lambda: dict(
+        camera_angle=35.0, position_relative_to_frame=[0.1, 0.0, 0.0], fov=120.0, resolution=[640, 480]))
     # ordered object_list for the collision pass (components.py:198-214): tuples
     # (type, x, y, z, radius, height) with type 0 = Ground, 1 = Cylinder, 2 = Target sphere; max 8
     objects: tuple = ()
@@ -250,6 +258,10 @@ def params_from_dict(cfg: Dict[str, Any], yaml_dir: str = _DATA_DIR, mode: Any =
     )
     if "force_multiplier_pid" in drone:                                          # params.yaml:55-62
         p.force_multiplier_pid = {k: float(v) for k, v in drone["force_multiplier_pid"].items()}
+    p.keep_distance = float(drone.get("keep_distance", p.keep_distance))                       # components.py:117-118
+    p.UWB_sensor_max_range = float(drone.get("UWB_sensor_max_range", p.UWB_sensor_max_range))
+    p.point_and_shoot.update(cfg.get("point_and_shoot") or {})                                 # components.py:114-116
+    p.camera.update(cfg.get("camera") or {})                                                   # components.py:107-111
     # 5 % throttle floor / full throttle, components.py:139-142
     p.min_throttle_in_force = float(p.thrust_from_stick(-1 + 5 / 100 * 2))
     p.max_throttle_in_force = float(p.thrust_from_stick(1.0))

@@ -314,7 +314,7 @@ typedef struct fpv_env* fpv_handle_t;
 
 int fpv_abi_version(void);
 /* sizeof of the ABI structs as this library was compiled (0 fpv_params_t, 1 fpv_buffers_t, 2 fpv_objects_t,
- * 3 fpv_pid_params_t, 4 fpv_cache_model_t, 5 fpv_gate_course_t, 6 fpv_range_scan_t, 7 fpv_depth_render_t):
+ * 3 fpv_pid_params_t, 4 fpv_cache_model_t, 5 fpv_gate_course_t, 6 fpv_range_scan_t, 7 fpv_depth_render_t, 8 fpv_chase_t):
  * lets a foreign-language binding verify its struct declarations at load time */
 int fpv_sizeof(int which);
 /* rows of the state matrix for a mode (FPV_DRONE_ROWS / FPV_RACER_ROWS), or FPV_EINVAL */
@@ -709,6 +709,65 @@ int fpv_pid_reset(float* pid_state, int64_t ld, int64_t n, const uint8_t* mask, 
  * error_out[i] (PID.error).  pid_state rows hold integral, prev_derivative, previous_error, is_first. */
 int fpv_pid_call(const fpv_pid_params_t* params, float* pid_state, int64_t ld, int64_t n, const float* current,
                  const float* target, float target_scalar, float* out, float* error_out, int device, void* stream);
+
+/* ---- Target chase: the reference's vision guidance law for N drones (functions and one struct only - FPV_ABI_VERSION, fpv_params_t
+ * and fpv_buffers_t are those of ABI 9) -------------------------------------------------------------------------------------------
+ * Drone.calculate_needed_force_orientation(pixel, target, ref_frame, mode) (components.py:258-304) fed by the pixel at which the
+ * drone's camera sees the target (simulator.py:102-110): one kernel, a lane per drone, reads p, v and q of an fp32 drone handle and
+ * the drone's four guidance-PID rows (FPV_PID_*, "components.PID" below), writes rotation[n][9] and thrust[n] in exactly the layout
+ * fpv_buffers_t.rotation_override / thrust_override take - the next fpv_step flies them.  The camera is the depth camera's
+ * (fpv_camera_t) without an image's size limits.  One shared target (centre, radius).  csrc/fpv_chase.h restates the law as
+ * computed and is the ONE definition the kernel (csrc/fpv_chase.hip) and fpv_chase_eval run: the same bits.
+ *   pixel: the caller's (x, y) per drone, or - pixel == NULL - the projection of the target's CENTRE (this build's definition of the
+ *     reference's centroid of splatted pixels), seen iff depth in (0, max_depth] and 0 <= x < W, 0 <= y < H.  A drone that does not
+ *     see the target (or whose given pixel is NaN) is not guided: thrust = NaN (fpv_step: not overridden), rotation = identity,
+ *     pixel_out = NaN, visible = 0, PID rows untouched.
+ *   defined where the reference gives NaN: |v| = 0 -> no virtual drag; F parallel to the second operand of the first cross
+ *     product -> that operand is replaced by the world x axis, then by the world y axis; F = 0 -> identity, thrust 0; a result
+ *     that is not finite -> not guided.  No finite state gives a NaN matrix.
+ * Like the range scan and the depth camera it is a kernel of its own: the state, the step counter and the rotation of the
+ * traversal are left alone.  It moves 112 bytes per drone (10 state floats + 4 PID rows read, 4 PID rows + 10 floats written),
+ * 120 with a supplied pixel. */
+#define FPV_CHASE_MAX_SIDE 16384
+enum { FPV_CHASE_WORLD = 0, FPV_CHASE_DRONE = 1 };            /* ref_frame = 'world' / 'drone' */
+enum { FPV_CHASE_LEVEL = 0, FPV_CHASE_FRONTARGET = 1 };       /* mode = 'level' / 'frontarget' */
+typedef struct fpv_chase {
+    uint32_t struct_size;            /* sizeof(fpv_chase_t) = fpv_sizeof(8) */
+    int32_t  width, height;          /* written by fpv_chase_derive: 1..FPV_CHASE_MAX_SIDE */
+    int32_t  ref_frame;              /* FPV_CHASE_WORLD / FPV_CHASE_DRONE */
+    int32_t  mode;                   /* FPV_CHASE_LEVEL / FPV_CHASE_FRONTARGET */
+    int32_t  _reserved;
+    double   focal_length;           /* written by fpv_chase_derive, like relative_rotation (row-major) and relative_position */
+    double   relative_rotation[9];
+    double   relative_position[3];
+    double   max_depth;              /* reach of the reference's target-only image (simulator.py:102: 15), finite, > 0 */
+    double   mass;                   /* kg: g = (0, 0, -9.81 mass) */
+    double   virtual_drag_coefficient, virtual_lift_coefficient, tof_effective_distance;   /* params.yaml point_and_shoot */
+    double   keep_distance, UWB_sensor_max_range;                                            /* params.yaml drone */
+    float    target[3];              /* the target's centre ... */
+    float    target_radius;          /* ... and radius, >= 0 */
+    fpv_pid_params_t pid;            /* Drone.force_multiplier_pid (components.py:143-145) */
+    float*   pid_state;              /* [FPV_PID_ROWS][pid_ld], read and written; DEVICE for fpv_chase_guide, HOST for fpv_chase_eval (as */
+    int64_t  pid_ld;                 /* >= n                                                         every pointer below); 4-byte aligned */
+    const float* pixel;              /* [n][2] (x, y) or NULL = find the target; 8-byte aligned */
+    float*   rotation;               /* [n][9] row-major body -> world, 4-byte aligned */
+    float*   thrust;                 /* [n] newtons; NaN = not guided */
+    float*   pixel_out;              /* [n][2] or NULL: the pixel used (NaN, NaN when not seen); 8-byte aligned */
+    uint8_t* visible;                /* [n] or NULL: exactly 0 or 1 */
+} fpv_chase_t;
+/* Fills width, height, focal_length, relative_rotation and relative_position of *out (host arithmetic only; every other field is
+ * left alone).  FPV_EPARAM, by name: width or height outside 1..16384, fov outside (0, 180), a pitch or a relative position that is
+ * not finite. */
+int fpv_chase_derive(const fpv_camera_t* camera, fpv_chase_t* out);
+/* One call of the law for the handle's n drones at b->state / b->ld on `stream`, under the handle's device: allocates nothing,
+ * never synchronises, does not advance the step index and does not touch the rotation.  FPV_EINVAL / FPV_EALIGN / FPV_EPARAM, by
+ * name: fp16 state, a Racer handle, a wrong struct_size, width or height out of range, an unknown ref_frame or mode, camera numbers
+ * or constants that are not finite, max_depth or mass not positive, a negative target radius, PID constants fpv_pid_call would
+ * refuse, null pid_state / rotation / thrust, pid_ld < n, misaligned pointers; and in a library built without csrc/fpv_chase.hip. */
+int fpv_chase_guide(fpv_handle_t h, const fpv_buffers_t* b, const fpv_chase_t* s, void* stream);
+/* The kernel's own lane function on the host (no handle, no device): drone i of n at p[i][3] with velocity v[i][3] and attitude
+ * q[i][4] (wxyz); every pointer of *s is HOST memory. */
+int fpv_chase_eval(const fpv_chase_t* s, int64_t n, const float* p /*[n][3]*/, const float* v /*[n][3]*/, const float* q /*[n][4] wxyz*/);
 
 const char* fpv_last_error(void);
 const char* fpv_error_name(int code);

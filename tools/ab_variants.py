@@ -42,12 +42,12 @@ if a.build:
     for k in names:
         os.makedirs(OUT, exist_ok=True)
         out = os.path.join(OUT, f"libfpv_v_{k}.so")
-        from __graft_entry__ import HIPCC_FLAGS, HIP_SRCS_ALL
+        from __graft_entry__ import HIPCC_FLAGS, HIP_SRCS_BUILD
         flags, extra = list(HIPCC_FLAGS), [f for f in VARIANTS[k] if not f.startswith("PRELOAD=")]
         for f in VARIANTS[k]:
             if f.startswith("PRELOAD="):
                 flags = [("-amdgpu-kernarg-preload-count=" + f.split("=")[1]) if x.startswith("-amdgpu-kernarg-preload-count=") else x for x in flags]
-        subprocess.run(["/opt/rocm/bin/hipcc", *flags, *extra, "-o", out, *HIP_SRCS_ALL], check=True)
+        subprocess.run(["/opt/rocm/bin/hipcc", *flags, *extra, "-o", out, *HIP_SRCS_BUILD], check=True)
         print("built", out)
     sys.exit(0)
 import torch
