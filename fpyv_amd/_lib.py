@@ -37,6 +37,11 @@ DEPTH_ENCODINGS = {"metres": 0, "u8": 1}
 FPV_CHASE_MAX_SIDE = 16384    # fpv_chase_guide: no image is written, the camera may be 1..16384 pixels wide and high ("Target chase")
 CHASE_FRAMES = {"world": 0, "drone": 1}
 CHASE_MODES = {"level": 0, "frontarget": 1}
+FPV_TGT_ROWS = 8              # fpv_pursuit_step: targets[8][ld] (fpv_abi.h "Pursuit task")
+TGT_CX, TGT_CY, TGT_CZ, TGT_PATH_R, TGT_RADIUS, TGT_PREV_DIST, TGT_COUNT, TGT_SPAWNS = range(8)
+FPV_TGT_FRESH = 0x80000000    # bit 31 of the COUNT word: not advanced since it was set or respawned
+FPV_PURSUIT_OBS = 7           # rows of the target observation: R^T (t - p), R^T (v_target - v), dist
+FPV_PURSUIT_MAX_RESOLUTION = 65536
 FPV_HALF_PAIR_ROWS = 5
 FPV_HALF_HALVES = 11          # binary16 values per drone in state_h (5 pair rows + 1 half row)
 FPV_OBS_AOS_DIM = 16
@@ -56,7 +61,8 @@ EXPORTS = ("fpv_abi_version", "fpv_sizeof", "fpv_state_rows", "fpv_algorithmic_b
            "fpv_gates_derive", "fpv_set_gates", "fpv_gate_eval",
            "fpv_rays_derive", "fpv_range_scan", "fpv_range_eval",
            "fpv_camera_derive", "fpv_depth_render", "fpv_depth_eval",
-           "fpv_chase_derive", "fpv_chase_guide", "fpv_chase_eval")
+           "fpv_chase_derive", "fpv_chase_guide", "fpv_chase_eval",
+           "fpv_pursuit_derive", "fpv_pursuit_sample", "fpv_pursuit_step", "fpv_pursuit_reset", "fpv_pursuit_eval")
 
 
 class FpvParams(C.Structure):
@@ -279,6 +285,17 @@ class FpvChase(C.Structure):
                 ("thrust", C.c_void_p), ("pixel_out", C.c_void_p), ("visible", C.c_void_p)]
 
 
+class FpvPursuit(C.Structure):
+    """fpv_pursuit_t: the path table, the rewards, the spawn box and the flags of a pursuit call, the target rows and the optional
+    outputs (device for fpv_pursuit_step / _reset, host for fpv_pursuit_eval), and the optional guidance law (a fpv_chase_t)."""
+    _fields_ = [("struct_size", C.c_uint32), ("path_resolution", C.c_int32), ("advance", C.c_int32), ("respawn_on_done", C.c_int32),
+                ("add_to_reward", C.c_int32), ("_reserved", C.c_int32), ("spawn_seed", C.c_uint64), ("dt", C.c_double),
+                ("capture_distance", C.c_double), ("progress", C.c_double), ("capture", C.c_double), ("spawn_lo", C.c_double * 3),
+                ("spawn_hi", C.c_double * 3), ("radius_lo", C.c_double), ("radius_hi", C.c_double), ("targets", C.c_void_p),
+                ("targets_ld", C.c_int64), ("circle", C.c_void_p), ("obs", C.c_void_p), ("obs_ld", C.c_int64), ("position", C.c_void_p),
+                ("position_ld", C.c_int64), ("event", C.c_void_p), ("reward_out", C.c_void_p), ("guide", C.POINTER(FpvChase))]
+
+
 class FpvCacheModel(C.Structure):
     """fpv_cache_model_t: what a device says about itself, held against the cache model of the rotation / row stride."""
     _fields_ = [("struct_size", C.c_uint32), ("matches", C.c_int32), ("compute_units", C.c_int32), ("xcds", C.c_int32),
@@ -375,11 +392,16 @@ def lib() -> C.CDLL:
     L.fpv_chase_derive.argtypes = [C.POINTER(FpvCamera), C.POINTER(FpvChase)]
     L.fpv_chase_guide.argtypes = [vp, pb, C.POINTER(FpvChase), vp]
     L.fpv_chase_eval.argtypes = [C.POINTER(FpvChase), i64, vp, vp, vp]
+    L.fpv_pursuit_derive.argtypes = [C.c_int32, vp]
+    L.fpv_pursuit_sample.argtypes = [C.POINTER(FpvPursuit), C.c_uint64, C.c_uint32, vp, C.POINTER(C.c_uint32)]
+    L.fpv_pursuit_step.argtypes = [vp, pb, C.POINTER(FpvPursuit), vp]
+    L.fpv_pursuit_reset.argtypes = [vp, pb, C.POINTER(FpvPursuit), vp, vp]
+    L.fpv_pursuit_eval.argtypes = [C.POINTER(FpvPursuit), i64, C.c_uint64, vp, vp, vp, vp, vp, C.c_int]
     if L.fpv_abi_version() != FPV_ABI_VERSION:
         raise ImportError(f"libfpv_hip.so ABI {L.fpv_abi_version()} != binding {FPV_ABI_VERSION} - rebuild the library "
                           "(`python -c 'import __graft_entry__ as g; g.build()'`)")
     for which, struct in ((0, FpvParams), (1, FpvBuffers), (2, FpvObjects), (3, FpvPidParams), (4, FpvCacheModel), (5, FpvGateCourse),
-                          (6, FpvRangeScan), (7, FpvDepthRender), (8, FpvChase)):
+                          (6, FpvRangeScan), (7, FpvDepthRender), (8, FpvChase), (10, FpvPursuit)):
         if L.fpv_sizeof(which) != C.sizeof(struct):
             raise ImportError(f"{struct.__name__}: ctypes declares {C.sizeof(struct)} bytes, libfpv_hip.so has "
                               f"{L.fpv_sizeof(which)} - _lib.py and include/fpv_abi.h are out of step")

@@ -67,10 +67,12 @@ struct FpvChaseOut { float rot[9]; float thrust, u, v; bool seen, guided; };
 
 FPV_HD bool fpv_chase_finite(float x) { return fabsf(x) <= 3.402823466e+38f; }
 
-// One drone.  have_pixel: (pu, pv) is the caller's pixel; else it is computed.  integ / dflt / last / first are the lane's PID rows
-// (FPV_PID_*), advanced only when o.guided.
-FPV_HD void fpv_chase_lane(const FpvChaseK& K, float px, float py, float pz, float vx, float vy, float vz, FpvQuat q, bool have_pixel,
-                           float pu, float pv, float& integ, float& dflt, float& last, float& first, FpvChaseOut& o)
+// One drone against the target of centre (tcx, tcy, tcz) and radius tr (K.tc / K.tr are not read: the pursuit task, fpv_pursuit.h,
+// passes each drone's own target).  have_pixel: (pu, pv) is the caller's pixel; else it is computed.  integ / dflt / last / first
+// are the lane's PID rows (FPV_PID_*), advanced only when o.guided.
+FPV_HD void fpv_chase_lane_at(const FpvChaseK& K, float tcx, float tcy, float tcz, float tr, float px, float py, float pz, float vx,
+                              float vy, float vz, FpvQuat q, bool have_pixel, float pu, float pv, float& integ, float& dflt, float& last,
+                              float& first, FpvChaseOut& o)
 {
     const float qnan = fpv_bits_f32(0x7fc00000u);
     const FpvRot R = fpv_rot(q);
@@ -83,7 +85,7 @@ FPV_HD void fpv_chase_lane(const FpvChaseK& K, float px, float py, float pz, flo
         const float ox = fmaf(R.r00, K.rel[0], fmaf(R.r01, K.rel[1], fmaf(R.r02, K.rel[2], px)));
         const float oy = fmaf(R.r10, K.rel[0], fmaf(R.r11, K.rel[1], fmaf(R.r12, K.rel[2], py)));
         const float oz = fmaf(R.r20, K.rel[0], fmaf(R.r21, K.rel[1], fmaf(R.r22, K.rel[2], pz)));
-        const float wx = K.tc[0] - ox, wy = K.tc[1] - oy, wz = K.tc[2] - oz;
+        const float wx = tcx - ox, wy = tcy - oy, wz = tcz - oz;
         const float bx = fmaf(R.r00, wx, fmaf(R.r10, wy, R.r20 * wz));      // R^T (c - o)
         const float by = fmaf(R.r01, wx, fmaf(R.r11, wy, R.r21 * wz));
         const float bz = fmaf(R.r02, wx, fmaf(R.r12, wy, R.r22 * wz));
@@ -112,8 +114,8 @@ FPV_HD void fpv_chase_lane(const FpvChaseK& K, float px, float py, float pz, flo
     const float k = fmaf(wx, dx, fmaf(wy, dy, wz * dz)) / (s == 0.0f ? 1.0f : s);
     const float drag = s == 0.0f ? 0.0f : -(K.vdrag * ((1.0f - k) * 0.5f) * s);
     const float lift = pz < K.tof ? -(K.tof - pz) * K.vlift * (1.0f + fabsf(vz)) : 0.0f;
-    const float tx = px - K.tc[0], ty = py - K.tc[1], tz = pz - K.tc[2];
-    const float far = fpv_sqrt_flushed(fmaf(tx, tx, fmaf(ty, ty, tz * tz))) - K.tr;
+    const float tx = px - tcx, ty = py - tcy, tz = pz - tcz;
+    const float far = fpv_sqrt_flushed(fmaf(tx, tx, fmaf(ty, ty, tz * tz))) - tr;
     const float dist = far < K.uwb ? far : K.uwb;
     float i2 = integ, l2 = last, d2 = dflt;
     const float m = fpv_clamp(fpv_pid_axis<float, 1>(K.pid, 0, dist, K.keep, first != 0.0f, i2, l2, d2), K.pid.min_output, K.pid.max_output);
@@ -153,6 +155,13 @@ FPV_HD void fpv_chase_lane(const FpvChaseK& K, float px, float py, float pz, flo
     o.thrust = o.guided ? fn : qnan;
     o.u = seen ? u : qnan;
     o.v = seen ? v : qnan;
+}
+
+// One drone against the call's shared target K.tc / K.tr
+FPV_HD void fpv_chase_lane(const FpvChaseK& K, float px, float py, float pz, float vx, float vy, float vz, FpvQuat q, bool have_pixel,
+                           float pu, float pv, float& integ, float& dflt, float& last, float& first, FpvChaseOut& o)
+{
+    fpv_chase_lane_at(K, K.tc[0], K.tc[1], K.tc[2], K.tr, px, py, pz, vx, vy, vz, q, have_pixel, pu, pv, integ, dflt, last, first, o);
 }
 
 // Host: the camera numbers of a chase from a camera (the arithmetic of DESIGN 3.8's derive, without an image's limits): double.

@@ -38,6 +38,7 @@
 #include "fpv_range.h"
 #include "fpv_depth.h"
 #include "fpv_chase.h"
+#include "fpv_pursuit.h"
 
 namespace {
 
@@ -866,6 +867,11 @@ extern "C" __attribute__((weak, visibility("hidden"))) void* fpv_depth_render_ke
 // fpv_chase_eval say so when they are absent): one FpvChaseArgs.
 extern "C" __attribute__((weak, visibility("hidden"))) void* fpv_chase_kernel_fn(int pixel);
 extern "C" __attribute__((weak, visibility("hidden"))) void fpv_chase_eval_host(const FpvChaseArgs* A, const float* p, const float* v, const float* q);
+// The kernels of csrc/fpv_pursuit.hip ([guidance law][reset call]) and its host loop, weak in the same way (fpv_pursuit_step, _reset
+// and _eval say so when they are absent): one FpvPursuitArgs.
+extern "C" __attribute__((weak, visibility("hidden"))) void* fpv_pursuit_kernel_fn(int guide, int reset);
+extern "C" __attribute__((weak, visibility("hidden"))) void fpv_pursuit_eval_host(const FpvPursuitArgs* A, const float* p, const float* v, const float* q,
+                                                                                  int guide, int reset);
 
 namespace {
 
@@ -1431,7 +1437,8 @@ int fpv_sizeof(int which)
         case 6: return (int)sizeof(fpv_range_scan_t);
         case 7: return (int)sizeof(fpv_depth_render_t);
         case 8: return (int)sizeof(fpv_chase_t);
-        default: return fail(FPV_EINVAL, "fpv_sizeof: 0 = fpv_params_t, 1 = fpv_buffers_t, 2 = fpv_objects_t, 3 = fpv_pid_params_t, 4 = fpv_cache_model_t, 5 = fpv_gate_course_t, 6 = fpv_range_scan_t, 7 = fpv_depth_render_t, 8 = fpv_chase_t");
+        case 10: return (int)sizeof(fpv_pursuit_t);        // 9 stays refused: the tests of six features hold it to "no such struct"
+        default: return fail(FPV_EINVAL, "fpv_sizeof: 0 = fpv_params_t, 1 = fpv_buffers_t, 2 = fpv_objects_t, 3 = fpv_pid_params_t, 4 = fpv_cache_model_t, 5 = fpv_gate_course_t, 6 = fpv_range_scan_t, 7 = fpv_depth_render_t, 8 = fpv_chase_t, 10 = fpv_pursuit_t");
     }
 }
 
@@ -1906,6 +1913,144 @@ int fpv_chase_eval(const fpv_chase_t* s, int64_t n, const float* p, const float*
     rc = chase_args(s, n, &A);
     if (rc != FPV_OK) return rc;
     fpv_chase_eval_host(&A, p, v, q);
+    return FPV_OK;
+}
+
+int fpv_pursuit_derive(int32_t resolution, float* circle_out_host)
+{
+    if (!circle_out_host) return fail(FPV_EINVAL, "null argument");
+    if (resolution < 1 || resolution > FPV_PURSUIT_MAX_RESOLUTION)
+        return fail(FPV_EPARAM, "path_resolution must be 1.." + std::to_string(FPV_PURSUIT_MAX_RESOLUTION) + ", not " + std::to_string(resolution));
+    // numpy.linspace(0, 2 pi, K + 1)[:-1] (helper_functions.py:152): theta_j = j * (2 pi / K)
+    const double step = 2.0 * M_PI / (double)resolution;
+    for (int32_t j = 0; j < resolution; ++j) {
+        circle_out_host[2 * j] = (float)cos((double)j * step);
+        circle_out_host[2 * j + 1] = (float)sin((double)j * step);
+    }
+    return FPV_OK;
+}
+
+namespace {
+
+const char kPursuitAbsent[] = "the pursuit task is not in this build (the library was linked without csrc/fpv_pursuit.hip)";
+
+// the constants of the respawn draw, checked: what fpv_pursuit_sample needs and the first part of pursuit_args
+int pursuit_spawn(const fpv_pursuit_t* s, FpvPursuitK* P)
+{
+    if (s->struct_size != sizeof(fpv_pursuit_t)) return fail(FPV_EINVAL, "fpv_pursuit_t.struct_size does not match this library");
+    if (s->path_resolution < 1 || s->path_resolution > FPV_PURSUIT_MAX_RESOLUTION)
+        return fail(FPV_EPARAM, "path_resolution must be 1.." + std::to_string(FPV_PURSUIT_MAX_RESOLUTION) + ", not " + std::to_string(s->path_resolution));
+    memset(P, 0, sizeof(*P));
+    for (int k = 0; k < 4; ++k) {
+        const double lo = k < 3 ? s->spawn_lo[k] : s->radius_lo, hi = k < 3 ? s->spawn_hi[k] : s->radius_hi;
+        if (!isfinite(lo) || !isfinite(hi)) return fail(FPV_EPARAM, k < 3 ? "the spawn box is not finite" : "the radius range is not finite");
+        if (hi < lo) return fail(FPV_EPARAM, k < 3 ? "the spawn box has hi < lo" : "the radius range has hi < lo");
+        P->lo[k] = (float)lo; P->span[k] = (float)(hi - lo);
+    }
+    if (s->radius_lo < 0.0) return fail(FPV_EPARAM, "a target's radius must not be negative");
+    P->seed_lo = (uint32_t)s->spawn_seed; P->seed_hi = (uint32_t)(s->spawn_seed >> 32);
+    P->resolution = (uint32_t)s->path_resolution;
+    return FPV_OK;
+}
+
+// the uniform constants of a call and its buffers, checked (n: the drones the buffers must hold; gid: the first drone's global id;
+// reward: the cells add_to_reward adds to, not read by a reset call): FPV_OK or the error
+int pursuit_args(const fpv_pursuit_t* s, int64_t n, uint64_t gid, float* reward, bool reset, FpvPursuitArgs* A)
+{
+    FpvPursuitK P;
+    int rc = pursuit_spawn(s, &P);
+    if (rc != FPV_OK) return rc;
+    const double four[4] = {s->dt, s->capture_distance, s->progress, s->capture};
+    const char* const names[4] = {"dt", "capture_distance", "progress", "capture"};
+    for (int k = 0; k < 4; ++k)
+        if (!isfinite(four[k])) return fail(FPV_EPARAM, std::string(names[k]) + " is not finite");
+    if (!(s->dt > 0.0)) return fail(FPV_EPARAM, "dt must be positive");
+    if (s->capture_distance < 0.0) return fail(FPV_EPARAM, "capture_distance must not be negative");
+    if (!s->targets) return fail(FPV_EINVAL, "fpv_pursuit_t.targets is null");
+    if (!s->circle) return fail(FPV_EINVAL, "fpv_pursuit_t.circle is null");
+    if (s->targets_ld < n) return fail(FPV_EALIGN, "fpv_pursuit_t.targets_ld is smaller than the number of drones");
+    if ((uintptr_t)s->targets & 15) return fail(FPV_EALIGN, "targets must be 16-byte aligned");
+    if ((uintptr_t)s->circle & 7) return fail(FPV_EALIGN, "circle must be 8-byte aligned");
+    if (((uintptr_t)s->obs & 3) || ((uintptr_t)s->position & 3) || ((uintptr_t)s->reward_out & 3)) return fail(FPV_EALIGN, "obs, position and reward_out must be 4-byte aligned");
+    if (s->obs && s->obs_ld < n) return fail(FPV_EALIGN, "fpv_pursuit_t.obs_ld is smaller than the number of drones");
+    if (s->position && s->position_ld < n) return fail(FPV_EALIGN, "fpv_pursuit_t.position_ld is smaller than the number of drones");
+    if (!reset && s->add_to_reward && !reward) return fail(FPV_EINVAL, "add_to_reward needs fpv_buffers_t.reward");
+    memset(A, 0, sizeof(*A));
+    if (s->guide) {
+        FpvChaseArgs C;
+        fpv_chase_t g = *s->guide;
+        g.target[0] = g.target[1] = g.target[2] = 0.0f; g.target_radius = 0.0f; g.pixel = nullptr;     // ignored: not checked
+        rc = chase_args(&g, n, &C);
+        if (rc != FPV_OK) return rc;
+        A->K = C.K; A->pid_state = C.pid_state; A->pid_ld = C.pid_ld; A->rotation = C.rotation; A->thrust = C.thrust;
+        A->pixel_out = C.pixel_out; A->visible = C.visible;
+    }
+    P.dt = (float)s->dt; P.capture_distance = (float)s->capture_distance; P.progress = (float)s->progress; P.capture = (float)s->capture;
+    P.gid_lo = (uint32_t)gid; P.gid_hi = (uint32_t)(gid >> 32);
+    P.advance = s->advance != 0; P.respawn_on_done = s->respawn_on_done != 0; P.add_to_reward = s->add_to_reward != 0;
+    A->P = P;
+    A->targets = s->targets; A->tld = s->targets_ld; A->circle = s->circle; A->obs = s->obs; A->obs_ld = s->obs_ld;
+    A->position = s->position; A->pos_ld = s->position_ld; A->event = s->event; A->reward_out = s->reward_out; A->n = n;
+    return FPV_OK;
+}
+
+int pursuit_launch(fpv_handle_t h, const fpv_buffers_t* b, const fpv_pursuit_t* s, const uint8_t* flags, bool reset, void* stream)
+{
+    if (fpv_pursuit_kernel_fn == nullptr) return fail(FPV_EINVAL, kPursuitAbsent);
+    if (!h) return fail(FPV_EINVAL, "null handle");
+    if (!b || !s) return fail(FPV_EINVAL, "null argument");
+    if (h->mode != FPV_MODE_DRONE) return fail(FPV_EINVAL, "the pursuit task is the Drone's chase: not for a Racer handle");
+    if (h->K.flags & FPV_FLAG_FP16_STATE)
+        return fail(FPV_EINVAL, "the pursuit task cannot read fp16 state (FPV_FLAG_FP16_STATE): a reader of the packed quaternion is the follow-up");
+    if (!b->state) return fail(FPV_EINVAL, "fpv_buffers_t.state is null");
+    if (b->ld < h->n) return fail(FPV_EALIGN, "fpv_buffers_t.ld is smaller than the number of drones");
+    FpvPursuitArgs A;
+    const int rc = pursuit_args(s, h->n, ((uint64_t)h->K.noise.id_hi << 32) | h->K.noise.id_lo, b->reward, reset, &A);
+    if (rc != FPV_OK) return rc;
+    A.state = b->state; A.ld = b->ld; A.done = flags;
+    if (!reset && s->add_to_reward) { A.reward = b->reward; A.ep_return = b->ep_return; }
+    const DeviceGuard dev(h->device);
+    if (dev.rc != FPV_OK) return dev.rc;
+    void* arg = &A;
+    return launch_args("pursuit kernel launch", fpv_pursuit_kernel_fn(s->guide != nullptr, reset), blocks_for(h->n, kStepBlock), dim3(kStepBlock),
+                       (hipStream_t)stream, &arg);
+}
+
+}  // namespace
+
+int fpv_pursuit_sample(const fpv_pursuit_t* s, uint64_t global_id, uint32_t respawn_index, float out[4], uint32_t* phase_out)
+{
+    if (!s || !out || !phase_out) return fail(FPV_EINVAL, "null argument");
+    FpvPursuitK P;
+    const int rc = pursuit_spawn(s, &P);
+    if (rc != FPV_OK) return rc;
+    fpv_pursuit_draw(P, global_id, respawn_index & 0xffffu, out, out[3], *phase_out);
+    return FPV_OK;
+}
+
+int fpv_pursuit_step(fpv_handle_t h, const fpv_buffers_t* b, const fpv_pursuit_t* s, void* stream)
+{
+    return pursuit_launch(h, b, s, b ? b->done : nullptr, false, stream);
+}
+
+int fpv_pursuit_reset(fpv_handle_t h, const fpv_buffers_t* b, const fpv_pursuit_t* s, const uint8_t* mask, void* stream)
+{
+    return pursuit_launch(h, b, s, mask, true, stream);
+}
+
+int fpv_pursuit_eval(const fpv_pursuit_t* s, int64_t n, uint64_t drone_id_offset, const float* p, const float* v, const float* q,
+                     const uint8_t* done_or_mask, float* reward, int reset)
+{
+    if (fpv_pursuit_eval_host == nullptr) return fail(FPV_EINVAL, kPursuitAbsent);
+    if (!v) return fail(FPV_EINVAL, "null argument");
+    int rc = check_eval_args(s, n, p, q);
+    if (rc != FPV_OK) return rc;
+    FpvPursuitArgs A;
+    rc = pursuit_args(s, n, drone_id_offset, reward, reset != 0, &A);
+    if (rc != FPV_OK) return rc;
+    A.done = done_or_mask;
+    if (!reset && s->add_to_reward) A.reward = reward;
+    fpv_pursuit_eval_host(&A, p, v, q, s->guide != nullptr, reset);
     return FPV_OK;
 }
 

@@ -213,6 +213,17 @@ class _Handle:
     def _depth_render_raw(self, render: "_lib.FpvDepthRender", stream: Optional[torch.cuda.Stream] = None) -> None:
         self._sensor_raw(self._L.fpv_depth_render, render, stream)
 
+    def _pursuit_step_raw(self, stream: Optional[torch.cuda.Stream] = None) -> None:
+        """The pursuit call after a step of this handle's drones (fpv_pursuit_step): targets advanced, distance paid, captures
+        respawned, the target observed and - with guide= - the next step's override written"""
+        self._sensor_raw(self._L.fpv_pursuit_step, self._pursuit, stream)
+
+    def _pursuit_reset_raw(self, what: "_lib.FpvPursuit", mask: Optional[torch.Tensor]) -> None:
+        """The pursuit call after a reset of the lanes of `mask` (fpv_pursuit_reset), on torch's current stream"""
+        rc = self._L.fpv_pursuit_reset(self._handle, self._buf_ref, C.byref(what), mask.data_ptr() if mask is not None else None, self._stream())
+        if rc < 0:
+            _lib.check(rc)
+
     def _widen(self, cols: int) -> torch.Tensor:
         """fp16 storage decoded into a fresh float32 [14, cols] tensor: one launch of fpv_widen_state on torch's current stream,
         a copy valid for as long as the caller keeps it."""
@@ -231,7 +242,7 @@ class _Batch(_Handle):
                  with_action_out: bool = False, kahan_position: bool = False, per_drone_reset_pose: bool = False,
                  per_drone_physics: bool = False, gates: Any = None, laps: int = 0, gate_rewards: Optional[Dict[str, float]] = None,
                  miss_is_done: bool = False, gate_obs: bool = True, gate_start: Any = None, range_rays: Any = None,
-                 range_max: float = 20.0, depth_camera: Any = None):
+                 range_max: float = 20.0, depth_camera: Any = None, pursuit: Any = None):
         if num_envs <= 0:
             raise ValueError("num_envs must be positive")
         device = torch.device(device)
@@ -338,6 +349,15 @@ class _Batch(_Handle):
                 self.gate_word = torch.zeros(self.n, **i32)
             self._course_kw = dict(laps=int(laps), gate_rewards=dict(gate_rewards or {}), miss_is_done=bool(miss_is_done))
             self.set_gates(gates)
+        # the pursuit task (fpv_pursuit_step; fpyv_amd.pursuit.PursuitTask): `target_rows` [8, ld] a target per drone (read and written
+        # by the call after every step and reset), `target_obs_rows` [7, ld], `target_position_rows` [3, ld], `target_event_u8` [n] and
+        # `pursuit_reward` [n] its outputs; with guide= `pursuit_pid_rows` [4, ld] and `pursuit_guidance` = (rotation_matrix
+        # [n, 3, 3], thrust_force [n]) of the last call, in the layout the step's override reads
+        self.pursuit = pursuit
+        self.target_rows = self.target_obs_rows = self.target_position_rows = self.target_event_u8 = self.pursuit_reward = None
+        self.pursuit_pid_rows = self.pursuit_guidance = self._pursuit = self._pursuit_set = self._pursuit_chase = None
+        if pursuit is not None:
+            self._init_pursuit(pursuit)
 
     # -- plumbing ---------------------------------------------------------------------------------
     def _fill_buffers(self) -> None:
@@ -419,8 +439,9 @@ class _Batch(_Handle):
 
     # -- checkpoint / resume (the reference has none; state is just tensors here) ------------------
     _CKPT_TENSORS = ("state", "state_h", "reward", "done", "ep_return", "ep_length", "last_return",
-                     "last_length", "noise_state", "pos_comp", "reset_pose", "physics", "gate_word", "gate_start", "gate_desc")
-    _CKPT_ROW_TENSORS = ("state", "noise_state", "pos_comp", "reset_pose", "physics")        # [rows, ld]: stored as their logical columns [rows, num_envs]
+                     "last_length", "noise_state", "pos_comp", "reset_pose", "physics", "gate_word", "gate_start", "gate_desc",
+                     "target_rows", "pursuit_pid_rows")
+    _CKPT_ROW_TENSORS = ("state", "noise_state", "pos_comp", "reset_pose", "physics", "target_rows", "pursuit_pid_rows")        # [rows, ld]: stored as their logical columns [rows, num_envs]
 
     def _state_h_views(self, t: Optional[torch.Tensor] = None, ld: Optional[int] = None):
         """(pair rows [5, ld, 2], thrust row [ld]) int16 views of an fp16 storage tensor laid out with row stride `ld`"""
@@ -569,6 +590,73 @@ class _Batch(_Handle):
         """[num_envs, 6] view: the next gate in the drone's body frame, R^T (c - p) and R^T n (None without gate_obs=True)"""
         return None if self.gate_obs_rows is None else self.gate_obs_rows[:, :self.n].t()
 
+    # -- pursuit task ------------------------------------------------------------------------------
+    def _init_pursuit(self, task) -> None:
+        f32 = dict(dtype=torch.float32, device=self.device)
+        self.target_rows = torch.from_numpy(task.rows(self.n, self.ld)).to(self.device)
+        self._pursuit_circle = torch.from_numpy(task.circle).to(self.device)
+        self.target_position_rows = torch.zeros((3, self.ld), **f32)
+        self.target_event_u8 = torch.zeros(self.n, dtype=torch.uint8, device=self.device)
+        self.pursuit_reward = torch.zeros(self.n, **f32)
+        s = task.derive(self.params.dt)
+        s.targets, s.targets_ld, s.circle = self.target_rows.data_ptr(), self.ld, self._pursuit_circle.data_ptr()
+        s.position, s.position_ld = self.target_position_rows.data_ptr(), self.ld
+        s.event, s.reward_out = self.target_event_u8.data_ptr(), self.pursuit_reward.data_ptr()
+        if task.obs:
+            self.target_obs_rows = torch.zeros((_lib.FPV_PURSUIT_OBS, self.ld), **f32)
+            s.obs, s.obs_ld = self.target_obs_rows.data_ptr(), self.ld
+        g = task.chase(self.params)
+        if g is not None:
+            self.pursuit_pid_rows = torch.zeros((_lib.FPV_PID_ROWS, self.ld), **f32)
+            self.pursuit_pid_rows[_lib.FPV_PID_ROWS - 1] = 1.0                  # is_first: a freshly reset PID
+            self.pursuit_guidance = (torch.zeros((self.n, 3, 3), **f32), torch.full((self.n,), float("nan"), **f32))
+            g.pid_state, g.pid_ld = self.pursuit_pid_rows.data_ptr(), self.ld
+            g.rotation, g.thrust = self.pursuit_guidance[0].data_ptr(), self.pursuit_guidance[1].data_ptr()
+            self._pursuit_chase = g
+            s.guide = C.pointer(g)
+        self._pursuit = s
+        # set_targets: the same call without a move and without a respawn - it only restarts the distance of the lanes it is given
+        self._pursuit_set = _lib.FpvPursuit.from_buffer_copy(s)
+        self._pursuit_set.advance = self._pursuit_set.respawn_on_done = 0
+
+    def set_targets(self, targets, mask=None) -> None:
+        """New targets for the drones of `mask` (None = all): what `PursuitTask(targets=)` takes, one per drone or one for all.
+        Their rows are uploaded on torch's current stream and the lanes rebase against them (fpv_pursuit_reset without a move or a
+        respawn): no progress is paid across the change, the episode's captures restart, a guide's PID restarts."""
+        if self._pursuit is None:
+            raise ValueError("this batch was built without pursuit=")
+        rows = torch.from_numpy(self.pursuit.rows(self.n, self.ld, targets)).to(self.device)
+        m = None
+        if mask is not None:
+            m = torch.as_tensor(mask, device=self.device).to(torch.uint8).contiguous()
+            if m.shape != (self.n,):
+                raise ValueError("mask must have shape (num_envs,)")
+            cells, mine = rows.view(torch.int32), self.target_rows.view(torch.int32)     # (words: COUNT and SPAWNS are no floats)
+            cells[:, :self.n] = torch.where(m.bool(), cells[:, :self.n], mine[:, :self.n])
+        self.target_rows.copy_(rows)
+        self._pursuit_reset_raw(self._pursuit_set, m)
+        self._keepalive_targets = m
+
+    @property
+    def target_obs(self) -> Optional[torch.Tensor]:
+        """[num_envs, 7] view: the drone's target in its body frame - R^T (t - p), R^T (v_target - v), dist (None with obs=False)"""
+        return None if self.target_obs_rows is None else self.target_obs_rows[:, :self.n].t()
+
+    @property
+    def target_position(self) -> Optional[torch.Tensor]:
+        """[num_envs, 3] view: every drone's target in the world frame after the last call"""
+        return None if self.target_position_rows is None else self.target_position_rows[:, :self.n].t()
+
+    @property
+    def target_event(self) -> Optional[torch.Tensor]:
+        """[num_envs] uint8: 1 where the last call was a capture"""
+        return self.target_event_u8
+
+    @property
+    def captures(self) -> Optional[torch.Tensor]:
+        """[num_envs] captures in the running episode"""
+        return None if self.target_rows is None else (self.target_rows[_lib.TGT_SPAWNS, :self.n].view(torch.int32) >> 16) & 0xFFFF
+
     # -- raw stepping -----------------------------------------------------------------------------
     def _reset_raw(self, mask=None, position=None, velocity=None, ypr=None) -> None:
         def dev3(x):
@@ -587,6 +675,8 @@ class _Batch(_Handle):
         _lib.check(self._L.fpv_reset(self._handle, C.byref(self._buf), ptr(m), ptr(pos), ptr(vel), ptr(ang),
                                      self._stream()))
         self._keepalive_reset = (pos, vel, ang, m)
+        if self._pursuit is not None:                   # the targets of the same lanes, after the state on the same stream
+            self._pursuit_reset_raw(self._pursuit, m)
 
     # -- per-drone physics ------------------------------------------------------------------------
     def _upload_physics(self, rows: np.ndarray, mask) -> None:
@@ -939,6 +1029,17 @@ class _Partition(_Handle):
         if self.parent._scan is not None:              # the parent's ray set on this partition's columns of the range rows
             self._scan = _lib.FpvRangeScan.from_buffer_copy(self.parent._scan)
             self._scan.ranges = self.parent._scan.ranges + 4 * lo
+        self._pursuit = self._pursuit_chase = None
+        pp = getattr(self.parent, "_pursuit", None)    # the parent's pursuit task on this partition's columns of its rows and outputs
+        if pp is not None:
+            t = self._pursuit = _lib.FpvPursuit.from_buffer_copy(pp)
+            t.targets, t.obs, t.position = pp.targets + 4 * lo, off(pp.obs, 4), off(pp.position, 4)
+            t.event, t.reward_out = off(pp.event, 1), off(pp.reward_out, 4)
+            pg = self.parent._pursuit_chase
+            if pg is not None:
+                g = self._pursuit_chase = _lib.FpvChase.from_buffer_copy(pg)
+                g.pid_state, g.rotation, g.thrust = pg.pid_state + 4 * lo, pg.rotation + 36 * lo, pg.thrust + 4 * lo
+                t.guide = C.pointer(g)
         self._render = None
         if self.parent._render is not None:            # the parent's camera on this partition's rows of the one image tensor
             r = self._render = _lib.FpvDepthRender.from_buffer_copy(self.parent._render)
@@ -1095,6 +1196,8 @@ class DroneBatch(_Batch):
                 # inherit this call's guidance matrix
                 self._buf.rotation_override = self._buf.thrust_override = None
                 self._override_keep = None
+        if self._pursuit is not None:
+            self._pursuit_step_raw()
         if not return_imu:
             return None
         if not self.fp16_state:
@@ -1212,7 +1315,7 @@ class FpvVecEnv:
     def __init__(self, params: Optional[DroneParams] = None, num_envs: int = 1, device: Any = "cuda:0",
                  mode: str = "drone", auto_reset: bool = True, track_episodes: bool = True,
                  wind: Sequence[float] = (0.0, 0.0, 0.0), object_list=(), partitions: int = 1, depth_every: int = 1,
-                 **batch_options: Any):
+                 guided: bool = False, **batch_options: Any):
         """`batch_options` go to DroneBatch / RacerBatch (stick_noise=, noise_seed=, drone_id_offset=,
         fp16_state=, with_obs_aos=, kahan_position=, with_done_bits=, per_drone_physics=, ...); `object_list` is the
         collision world of every step (fpyv_amd.objects); `partitions` > 1 enables step_async / step_wait.  `range_rays=`
@@ -1222,7 +1325,11 @@ class FpvVecEnv:
         `depth_every`-th step are followed by a render of `object_list` and the gate course on the same stream (each partition
         into its rows of the one tensor), `depth` [num_envs, H, W] and info["depth"] hold the result; `depth_every=0` never renders
         by itself - call `render_depth()`.  With `depth_every=1` the image always belongs to `obs`: a lane that auto-reset shows
-        its reset pose."""
+        its reset pose.  `pursuit=` (a fpyv_amd.pursuit.PursuitTask) gives every drone a target of its own: reset() and every
+        step are followed by the pursuit call on the same stream (before the scan and the render), which adds the task's payment
+        to `reward` and the episode return; `target_obs` [num_envs, 7], `target_position`, `target_event`, `captures` and
+        info["target_obs" | "target_event" | "captures"] hold the result.  With `PursuitTask(guide=...)`, `guided=True` flies
+        every step under the override the previous call wrote (`batch.pursuit_guidance`): the reference's chase loop."""
         if mode not in ("drone", "racer"):
             raise ValueError(f'mode must be "drone" or "racer", got {mode!r}')
         params = params if params is not None else load_params(fps=1000)
@@ -1259,6 +1366,15 @@ class FpvVecEnv:
                 # for the single chain at 2^20 drones - split phase is for closed loops, where the policy is what gets hidden)
                 self._part_views = [None] * len(self._parts)
         self.partitions = max(1, len(self._parts))
+        self.guided = bool(guided)
+        if self.guided:
+            g = getattr(self.batch, "pursuit_guidance", None)
+            if g is None:
+                raise ValueError("guided=True needs pursuit=PursuitTask(guide=...)")
+            # every step reads the override the last pursuit call wrote (what the library refuses to combine with it - a reset
+            # source, fp16 state, a Racer - it refuses at the step, by name)
+            for stepper, lo in [(self.batch, 0)] + [(P, P.lo) for P in self._parts]:
+                stepper._buf.rotation_override, stepper._buf.thrust_override = g[0].data_ptr() + 36 * lo, g[1].data_ptr() + 4 * lo
 
     @property
     def obs(self) -> torch.Tensor:
@@ -1329,6 +1445,27 @@ class FpvVecEnv:
         """[num_envs, 6] view of the gate observation rows (DroneBatch.gate_obs)"""
         return self.batch.gate_obs
 
+    def set_targets(self, targets, mask=None) -> None:
+        """DroneBatch.set_targets for the whole population (built with pursuit=), ordered after steps in flight like reset."""
+        self._whole_population(self.batch.set_targets, targets, mask)
+
+    @property
+    def target_obs(self) -> Optional[torch.Tensor]:
+        """[num_envs, 7] view of the target observation rows (DroneBatch.target_obs)"""
+        return self.batch.target_obs
+
+    @property
+    def target_position(self) -> Optional[torch.Tensor]:
+        return self.batch.target_position
+
+    @property
+    def target_event(self) -> Optional[torch.Tensor]:
+        return self.batch.target_event
+
+    @property
+    def captures(self) -> Optional[torch.Tensor]:
+        return self.batch.captures
+
     @property
     def ranges(self) -> Optional[torch.Tensor]:
         """[R, num_envs] view of the range rows after the last step or reset (None without range_rays=); `.T` is the
@@ -1358,7 +1495,10 @@ class FpvVecEnv:
         self._sense(self.batch, render=bool(self.depth_every))
 
     def _sense_after_step(self, stepper: _Handle, stream: Optional[torch.cuda.Stream] = None) -> None:
-        """every step of `stepper` is followed by a scan, every `depth_every`-th since the last reset() by a render"""
+        """every step of `stepper` is followed by the pursuit call (a batch built with pursuit=), then by a scan, every
+        `depth_every`-th since the last reset() by a render"""
+        if stepper._pursuit is not None:
+            stepper._pursuit_step_raw(stream)
         due = False
         if self.batch.depth is not None and self.depth_every:
             stepper._depth_steps += 1
@@ -1414,6 +1554,11 @@ class FpvVecEnv:
         if getattr(batch, "gate_word", None) is not None:              # a gate course: the race state after this step
             w = batch.gate_word[lo:hi]
             info["gates_passed"], info["gate_event"] = (w >> 10) & 0x3FFFFF, (w >> 8) & 3
+        if getattr(batch, "target_rows", None) is not None:            # the pursuit task: the target after this step's call
+            if batch.target_obs_rows is not None:
+                info["target_obs"] = batch.target_obs_rows[:, lo:hi].t()
+            info["target_event"] = batch.target_event_u8[lo:hi]
+            info["captures"] = (batch.target_rows[_lib.TGT_SPAWNS, lo:hi].view(torch.int32) >> 16) & 0xFFFF
         if getattr(batch, "range_rows", None) is not None:             # the range sensor: [R, columns] after this step's scan
             info["ranges"] = batch.range_rows[:, lo:hi]
         if getattr(batch, "depth", None) is not None:                  # the depth camera: [columns, H, W] after the last render

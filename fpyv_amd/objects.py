@@ -67,6 +67,8 @@ class Target:
         self.radius = float(radius)
         self._path = circular_path(self.position, **path) if path is not None else None
         self._count = 0
+        # what the pursuit task reads (fpyv_amd.pursuit): the centre of the path and its arguments; `_count` is the phase
+        self.center, self.path = self.position.copy(), (dict(path) if path is not None else None)
 
     def update(self) -> None:
         if self._path is not None:

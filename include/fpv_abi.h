@@ -769,6 +769,74 @@ int fpv_chase_guide(fpv_handle_t h, const fpv_buffers_t* b, const fpv_chase_t* s
  * q[i][4] (wxyz); every pointer of *s is HOST memory. */
 int fpv_chase_eval(const fpv_chase_t* s, int64_t n, const float* p /*[n][3]*/, const float* v /*[n][3]*/, const float* q /*[n][4] wxyz*/);
 
+/* ---- Pursuit task: every drone chases a target of its own (functions and one struct only - FPV_ABI_VERSION, fpv_params_t and
+ * fpv_buffers_t are those of ABI 9) -----------------------------------------------------------------------------------------------
+ * The reference's simulator (simulator.py:54-110) for N drones: generate_targets once, target.update() every iteration, the guidance
+ * law against the drone's target.  targets[FPV_TGT_ROWS][targets_ld] holds a target per drone in the state's column order (4-byte
+ * cells, caller-owned): the centre and the radius of its circular path (components.CircularPath; radius 0 = it stands still), the
+ * sphere's radius, the distance last measured, the word COUNT (bits 0..16: path index of the next update(), bit 31 FPV_TGT_FRESH: not
+ * advanced since it was set or respawned - such a target stands at that index and its first update() leaves it there) and the word
+ * SPAWNS (low 16 bits: respawns so far, high 16: captures in the current episode).  The unit circle is one shared table circle[K][2]
+ * (fpv_pursuit_derive).  One kernel of its own, a lane per drone, launched AFTER the step (the reference's order: update(), the law on
+ * the state the next step starts from, then the step): it advances the target, measures dist = |t - p| - radius, pays
+ * progress (previous dist - dist) and, when dist <= capture_distance, `capture` - then the target respawns in the spawn box (a
+ * Philox draw keyed by spawn_seed, the drone's global id and its respawn index only) and the jump of the distance is not paid -,
+ * observes the target in the body frame and, with `guide`, runs the target chase's law against the drone's own target and writes the
+ * next step's override.  A lane whose done byte is set (fpv_pursuit_step) or that is in the mask (fpv_pursuit_reset) REBASES: it pays
+ * nothing, clears its episode's captures, respawns when respawn_on_done, restarts its distance and (guide) its PID rows.
+ * csrc/fpv_pursuit.h states all of it as computed and is the ONE definition the kernel (csrc/fpv_pursuit.hip) and fpv_pursuit_eval
+ * run: the same bits.  The step kernels' object list, the range scan and the depth camera do not see these targets. */
+enum { FPV_TGT_CX = 0, FPV_TGT_CY, FPV_TGT_CZ, FPV_TGT_PATH_R, FPV_TGT_RADIUS, FPV_TGT_PREV_DIST, FPV_TGT_COUNT, FPV_TGT_SPAWNS, FPV_TGT_ROWS };
+#define FPV_TGT_FRESH 0x80000000u
+#define FPV_PURSUIT_OBS 7              /* rows of obs: R^T (t - p) (3), R^T (v_target - v) (3), dist */
+#define FPV_PURSUIT_MAX_RESOLUTION 65536
+typedef struct fpv_pursuit {
+    uint32_t struct_size;            /* sizeof(fpv_pursuit_t) = fpv_sizeof(10) (9 stays "no such struct") */
+    int32_t  path_resolution;        /* K: 1..FPV_PURSUIT_MAX_RESOLUTION (the reference's default: 5500) */
+    int32_t  advance;                /* 0: the targets are not moved by this call */
+    int32_t  respawn_on_done;        /* a rebasing lane draws a new target */
+    int32_t  add_to_reward;          /* fpv_pursuit_step adds the payment to b->reward (required then) and b->ep_return (when given) */
+    int32_t  _reserved;
+    uint64_t spawn_seed;
+    double   dt;                     /* > 0: the target's velocity is (t - t_previous) / dt */
+    double   capture_distance;       /* >= 0 */
+    double   progress, capture;      /* the rewards */
+    double   spawn_lo[3], spawn_hi[3];   /* box of a respawned target's centre, lo <= hi */
+    double   radius_lo, radius_hi;       /* range of its radius, 0 <= lo <= hi */
+    float*   targets;                /* [FPV_TGT_ROWS][targets_ld], 16-byte aligned; DEVICE for fpv_pursuit_step / _reset, HOST for */
+    int64_t  targets_ld;             /* >= n                                             fpv_pursuit_eval (as every pointer below) */
+    const float* circle;             /* [K][2] (cos, sin), 8-byte aligned: what fpv_pursuit_derive wrote */
+    float*   obs;                    /* [FPV_PURSUIT_OBS][obs_ld] or NULL */
+    int64_t  obs_ld;
+    float*   position;               /* [3][position_ld] or NULL: the target's world position */
+    int64_t  position_ld;
+    uint8_t* event;                  /* [n] or NULL: 1 = captured in this call */
+    float*   reward_out;             /* [n] or NULL: what the task paid in this call */
+    const fpv_chase_t* guide;        /* or NULL.  Given: its pid_state, rotation and thrust are required (and pixel_out / visible honoured), */
+} fpv_pursuit_t;                     /* its target, target_radius and pixel are ignored - the pixel is found by projection */
+/* circle_out_host[resolution][2] = (cos, sin)(2 pi j / resolution) as the reference's linspace takes the angles, computed in double
+ * and rounded once (host arithmetic only).  FPV_EPARAM: a resolution outside 1..65536. */
+int fpv_pursuit_derive(int32_t resolution, float* circle_out_host);
+/* The respawn draw of drone `global_id`'s respawn number `respawn_index` on the host (the kernel's own function): out[0..2] the
+ * centre, out[3] the radius, *phase_out the path index in [0, K).  Reads spawn_seed, the box, the radius range and path_resolution
+ * of *s. */
+int fpv_pursuit_sample(const fpv_pursuit_t* s, uint64_t global_id, uint32_t respawn_index, float out[4], uint32_t* phase_out);
+/* One call for the handle's n drones at b->state / b->ld on `stream`, under the handle's device: reads b->done (NULL = no lane
+ * rebases), adds to b->reward / b->ep_return when add_to_reward.  Allocates nothing, never synchronises, does not advance the step
+ * index and does not touch the rotation.  FPV_EINVAL / FPV_EALIGN / FPV_EPARAM, by name: fp16 state, a Racer handle, a wrong
+ * struct_size, path_resolution out of range, constants that are not finite, a box with hi < lo, a negative radius or
+ * capture_distance, dt <= 0, null targets / circle, targets_ld (obs_ld, position_ld) < n, misaligned pointers, add_to_reward without
+ * b->reward, everything fpv_chase_guide refuses for `guide`; and in a library built without csrc/fpv_pursuit.hip. */
+int fpv_pursuit_step(fpv_handle_t h, const fpv_buffers_t* b, const fpv_pursuit_t* s, void* stream);
+/* The reset call, after fpv_reset with the same mask: the lanes whose mask byte is non-zero (mask NULL = all) rebase; the others are
+ * not touched at all.  Pays nothing and does not read b->done / b->reward. */
+int fpv_pursuit_reset(fpv_handle_t h, const fpv_buffers_t* b, const fpv_pursuit_t* s, const uint8_t* mask, void* stream);
+/* The kernel's own lane function on the host (no handle, no device): drone i of n at p[i][3] with velocity v[i][3] and attitude
+ * q[i][4] (wxyz), global id drone_id_offset + i; done_or_mask [n] or NULL, reward [n] (read and written when add_to_reward, else may
+ * be NULL); reset != 0: the reset call.  Every pointer of *s is HOST memory. */
+int fpv_pursuit_eval(const fpv_pursuit_t* s, int64_t n, uint64_t drone_id_offset, const float* p /*[n][3]*/, const float* v /*[n][3]*/,
+                     const float* q /*[n][4] wxyz*/, const uint8_t* done_or_mask, float* reward, int reset);
+
 const char* fpv_last_error(void);
 const char* fpv_error_name(int code);
 /* Identifier of what stored bits mean, for checkpoints: 0 = the fp16 state storage words (FPV_FLAG_FP16_STATE), 1 = the
