@@ -62,7 +62,8 @@ EXPORTS = ("fpv_abi_version", "fpv_sizeof", "fpv_state_rows", "fpv_algorithmic_b
            "fpv_rays_derive", "fpv_range_scan", "fpv_range_eval",
            "fpv_camera_derive", "fpv_depth_render", "fpv_depth_eval",
            "fpv_chase_derive", "fpv_chase_guide", "fpv_chase_eval",
-           "fpv_pursuit_derive", "fpv_pursuit_sample", "fpv_pursuit_step", "fpv_pursuit_reset", "fpv_pursuit_eval")
+           "fpv_pursuit_derive", "fpv_pursuit_sample", "fpv_pursuit_step", "fpv_pursuit_reset", "fpv_pursuit_eval",
+           "fpv_pns_derive", "fpv_pns_guide", "fpv_pns_eval")
 
 
 class FpvParams(C.Structure):
@@ -285,6 +286,21 @@ class FpvChase(C.Structure):
                 ("thrust", C.c_void_p), ("pixel_out", C.c_void_p), ("visible", C.c_void_p)]
 
 
+class FpvPns(C.Structure):
+    """fpv_pns_t: the camera numbers fpv_chase_derive computes, the law's constants, frame and mode, the thrust limit and the inverse
+    thrust polynomial, the guidance PID's constants and rows, the prev_pixel rows, the optional pixels, targets, commands and restart
+    bytes, and the outputs (device for fpv_pns_guide, host for fpv_pns_eval; `target` is always host memory)."""
+    _fields_ = [("struct_size", C.c_uint32), ("width", C.c_int32), ("height", C.c_int32), ("ref_frame", C.c_int32), ("mode", C.c_int32),
+                ("_reserved", C.c_int32), ("focal_length", C.c_double), ("relative_rotation", C.c_double * 9),
+                ("relative_position", C.c_double * 3), ("max_depth", C.c_double), ("mass", C.c_double),
+                ("virtual_drag_coefficient", C.c_double), ("virtual_lift_coefficient", C.c_double), ("tof_effective_distance", C.c_double),
+                ("max_throttle_in_force", C.c_double), ("thrust2throttle_poly", C.c_double * 4), ("pid", FpvPidParams),
+                ("pid_state", C.c_void_p), ("pid_ld", C.c_int64), ("prev_pixel", C.c_void_p), ("prev_pixel_ld", C.c_int64),
+                ("pixel", C.c_void_p), ("target", C.c_void_p), ("target_rows", C.c_void_p), ("target_ld", C.c_int64),
+                ("action", C.c_void_p), ("restart", C.c_void_p), ("rotation", C.c_void_p), ("thrust", C.c_void_p),
+                ("pixel_velocity", C.c_void_p), ("limited", C.c_void_p), ("visible", C.c_void_p), ("throttle", C.c_void_p)]
+
+
 class FpvPursuit(C.Structure):
     """fpv_pursuit_t: the path table, the rewards, the spawn box and the flags of a pursuit call, the target rows and the optional
     outputs (device for fpv_pursuit_step / _reset, host for fpv_pursuit_eval), and the optional guidance law (a fpv_chase_t)."""
@@ -397,11 +413,14 @@ def lib() -> C.CDLL:
     L.fpv_pursuit_step.argtypes = [vp, pb, C.POINTER(FpvPursuit), vp]
     L.fpv_pursuit_reset.argtypes = [vp, pb, C.POINTER(FpvPursuit), vp, vp]
     L.fpv_pursuit_eval.argtypes = [C.POINTER(FpvPursuit), i64, C.c_uint64, vp, vp, vp, vp, vp, C.c_int]
+    L.fpv_pns_derive.argtypes = [C.POINTER(FpvCamera), C.POINTER(FpvPns)]
+    L.fpv_pns_guide.argtypes = [vp, pb, C.POINTER(FpvPns), vp]
+    L.fpv_pns_eval.argtypes = [C.POINTER(FpvPns), i64, vp, vp, vp]
     if L.fpv_abi_version() != FPV_ABI_VERSION:
         raise ImportError(f"libfpv_hip.so ABI {L.fpv_abi_version()} != binding {FPV_ABI_VERSION} - rebuild the library "
                           "(`python -c 'import __graft_entry__ as g; g.build()'`)")
     for which, struct in ((0, FpvParams), (1, FpvBuffers), (2, FpvObjects), (3, FpvPidParams), (4, FpvCacheModel), (5, FpvGateCourse),
-                          (6, FpvRangeScan), (7, FpvDepthRender), (8, FpvChase), (10, FpvPursuit)):
+                          (6, FpvRangeScan), (7, FpvDepthRender), (8, FpvChase), (10, FpvPursuit), (12, FpvPns)):
         if L.fpv_sizeof(which) != C.sizeof(struct):
             raise ImportError(f"{struct.__name__}: ctypes declares {C.sizeof(struct)} bytes, libfpv_hip.so has "
                               f"{L.fpv_sizeof(which)} - _lib.py and include/fpv_abi.h are out of step")

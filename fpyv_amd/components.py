@@ -2,9 +2,10 @@
 the per-drone step: `from fpyv_amd.components import Drone, Ground, Cylinder, Target, Gate, Trail, PID`.
 
     reference class (src/utils/components.py)      here
-    Drone   :72-248, :258-304                       fpyv_amd.env.DroneBatch  (N drones per object; `Drone(params)`
+    Drone   :72-248, :258-304, :312-387             fpyv_amd.env.DroneBatch  (N drones per object; `Drone(params)`
                                                     takes the same params dict, plus num_envs= / device=;
-                                                    calculate_needed_force_orientation is DESIGN 3.9)
+                                                    calculate_needed_force_orientation is DESIGN 3.9,
+                                                    point_and_shoot(pixel, action, ref_frame, mode) DESIGN 3.11)
     PID     :15-54                                  fpyv_amd.pid.PID         (N controllers per object)
     Ground  :646-683, Cylinder :685-729,            fpyv_amd.objects         (reference constructor signatures;
     Target  :753-778, Gate :780-831, Trail :631-644                           distance + normal only, Gate/Trail inert)

@@ -38,6 +38,7 @@
 #include "fpv_range.h"
 #include "fpv_depth.h"
 #include "fpv_chase.h"
+#include "fpv_pns.h"
 #include "fpv_pursuit.h"
 
 namespace {
@@ -867,6 +868,9 @@ extern "C" __attribute__((weak, visibility("hidden"))) void* fpv_depth_render_ke
 // fpv_chase_eval say so when they are absent): one FpvChaseArgs.
 extern "C" __attribute__((weak, visibility("hidden"))) void* fpv_chase_kernel_fn(int pixel);
 extern "C" __attribute__((weak, visibility("hidden"))) void fpv_chase_eval_host(const FpvChaseArgs* A, const float* p, const float* v, const float* q);
+// The kernels of csrc/fpv_pns.hip (with and without a supplied pixel) and its host loop, weak in the same way: one FpvPnsArgs.
+extern "C" __attribute__((weak, visibility("hidden"))) void* fpv_pns_kernel_fn(int pixel);
+extern "C" __attribute__((weak, visibility("hidden"))) void fpv_pns_eval_host(const FpvPnsArgs* A, const float* p, const float* v, const float* q);
 // The kernels of csrc/fpv_pursuit.hip ([guidance law][reset call]) and its host loop, weak in the same way (fpv_pursuit_step, _reset
 // and _eval say so when they are absent): one FpvPursuitArgs.
 extern "C" __attribute__((weak, visibility("hidden"))) void* fpv_pursuit_kernel_fn(int guide, int reset);
@@ -1438,7 +1442,8 @@ int fpv_sizeof(int which)
         case 7: return (int)sizeof(fpv_depth_render_t);
         case 8: return (int)sizeof(fpv_chase_t);
         case 10: return (int)sizeof(fpv_pursuit_t);        // 9 stays refused: the tests of six features hold it to "no such struct"
-        default: return fail(FPV_EINVAL, "fpv_sizeof: 0 = fpv_params_t, 1 = fpv_buffers_t, 2 = fpv_objects_t, 3 = fpv_pid_params_t, 4 = fpv_cache_model_t, 5 = fpv_gate_course_t, 6 = fpv_range_scan_t, 7 = fpv_depth_render_t, 8 = fpv_chase_t, 10 = fpv_pursuit_t");
+        case 12: return (int)sizeof(fpv_pns_t);            // 11 stays refused like 9
+        default: return fail(FPV_EINVAL, "fpv_sizeof: 0 = fpv_params_t, 1 = fpv_buffers_t, 2 = fpv_objects_t, 3 = fpv_pid_params_t, 4 = fpv_cache_model_t, 5 = fpv_gate_course_t, 6 = fpv_range_scan_t, 7 = fpv_depth_render_t, 8 = fpv_chase_t, 10 = fpv_pursuit_t, 12 = fpv_pns_t");
     }
 }
 
@@ -1913,6 +1918,109 @@ int fpv_chase_eval(const fpv_chase_t* s, int64_t n, const float* p, const float*
     rc = chase_args(s, n, &A);
     if (rc != FPV_OK) return rc;
     fpv_chase_eval_host(&A, p, v, q);
+    return FPV_OK;
+}
+
+int fpv_pns_derive(const fpv_camera_t* camera, fpv_pns_t* out)
+{
+    if (!camera || !out) return fail(FPV_EINVAL, "null argument");
+    fpv_chase_t c;
+    const int rc = fpv_chase_derive(camera, &c);
+    if (rc != FPV_OK) return rc;
+    out->width = c.width; out->height = c.height; out->focal_length = c.focal_length;
+    memcpy(out->relative_rotation, c.relative_rotation, sizeof c.relative_rotation);
+    memcpy(out->relative_position, c.relative_position, sizeof c.relative_position);
+    return FPV_OK;
+}
+
+namespace {
+
+const char kPnsAbsent[] = "point and shoot is not in this build (the library was linked without csrc/fpv_pns.hip)";
+
+// the uniform constants of a call and its buffers, checked (n: the drones the buffers must hold): FPV_OK or the error.  What the
+// struct shares with fpv_chase_t is checked by chase_args itself, on a fpv_chase_t holding those fields.
+int pns_args(const fpv_pns_t* s, int64_t n, FpvPnsArgs* A)
+{
+    if (s->struct_size != sizeof(fpv_pns_t)) return fail(FPV_EINVAL, "fpv_pns_t.struct_size does not match this library");
+    if (!s->pid_state) return fail(FPV_EINVAL, "fpv_pns_t.pid_state is null");
+    if (!s->prev_pixel) return fail(FPV_EINVAL, "fpv_pns_t.prev_pixel is null");
+    if (!s->rotation) return fail(FPV_EINVAL, "fpv_pns_t.rotation is null");
+    if (!s->thrust) return fail(FPV_EINVAL, "fpv_pns_t.thrust is null");
+    if (s->pid.struct_size != sizeof(fpv_pid_params_t)) return fail(FPV_EINVAL, "fpv_pns_t.pid.struct_size does not match this library");
+    if (s->pid_ld < n) return fail(FPV_EALIGN, "fpv_pns_t.pid_ld is smaller than the number of drones");
+    if (((uintptr_t)s->pixel & 7) || ((uintptr_t)s->pixel_velocity & 7)) return fail(FPV_EALIGN, "pixel and pixel_velocity must be 8-byte aligned");
+    fpv_chase_t c;
+    memset(&c, 0, sizeof c);
+    c.struct_size = sizeof c;
+    c.width = s->width; c.height = s->height; c.ref_frame = s->ref_frame; c.mode = s->mode; c.focal_length = s->focal_length;
+    memcpy(c.relative_rotation, s->relative_rotation, sizeof c.relative_rotation);
+    memcpy(c.relative_position, s->relative_position, sizeof c.relative_position);
+    c.max_depth = s->max_depth; c.mass = s->mass; c.virtual_drag_coefficient = s->virtual_drag_coefficient;
+    c.virtual_lift_coefficient = s->virtual_lift_coefficient; c.tof_effective_distance = s->tof_effective_distance;
+    c.pid = s->pid; c.pid_state = s->pid_state; c.pid_ld = s->pid_ld; c.rotation = s->rotation; c.thrust = s->thrust;
+    FpvChaseArgs C;
+    const int rc = chase_args(&c, n, &C);
+    if (rc != FPV_OK) return rc;
+    if (!isfinite(s->max_throttle_in_force) || !(s->max_throttle_in_force > 0.0)) return fail(FPV_EPARAM, "max_throttle_in_force must be finite and positive");
+    for (int k = 0; k < 4; ++k)
+        if (!isfinite(s->thrust2throttle_poly[k])) return fail(FPV_EPARAM, "thrust2throttle_poly is not finite");
+    if (s->target && s->target_rows) return fail(FPV_EINVAL, "both a shared target and target_rows are given: one target per call");
+    if (!s->pixel && !s->target && !s->target_rows) return fail(FPV_EINVAL, "pixel is null and neither target nor target_rows is given");
+    if (s->prev_pixel_ld < n) return fail(FPV_EALIGN, "fpv_pns_t.prev_pixel_ld is smaller than the number of drones");
+    if (s->target_rows && s->target_ld < n) return fail(FPV_EALIGN, "fpv_pns_t.target_ld is smaller than the number of drones");
+    if (((uintptr_t)s->prev_pixel & 3) || ((uintptr_t)s->target_rows & 3) || ((uintptr_t)s->throttle & 3))
+        return fail(FPV_EALIGN, "prev_pixel, target_rows and throttle must be 4-byte aligned");
+    if ((uintptr_t)s->action & 15) return fail(FPV_EALIGN, "action must be 16-byte aligned");
+    memset(A, 0, sizeof(*A));
+    FpvPnsK& K = A->K;
+    K.C = C.K;
+    K.fmax = (float)s->max_throttle_in_force;
+    for (int k = 0; k < 4; ++k) K.inv[k] = (float)s->thrust2throttle_poly[k];
+    if (s->target) {
+        for (int k = 0; k < 3; ++k) {
+            if (!isfinite(s->target[k])) return fail(FPV_EPARAM, "the target's centre is not finite");
+            K.tc[k] = s->target[k];
+        }
+    }
+    A->pid_state = s->pid_state; A->pid_ld = s->pid_ld; A->prev_pixel = s->prev_pixel; A->prev_ld = s->prev_pixel_ld; A->pixel = s->pixel;
+    A->target_rows = s->target_rows; A->target_ld = s->target_ld; A->action = s->action; A->restart = s->restart;
+    A->rotation = s->rotation; A->thrust = s->thrust; A->pixel_velocity = s->pixel_velocity; A->limited = s->limited;
+    A->visible = s->visible; A->throttle = s->throttle; A->n = n;
+    return FPV_OK;
+}
+
+}  // namespace
+
+int fpv_pns_guide(fpv_handle_t h, const fpv_buffers_t* b, const fpv_pns_t* s, void* stream)
+{
+    if (fpv_pns_kernel_fn == nullptr) return fail(FPV_EINVAL, kPnsAbsent);
+    if (!h) return fail(FPV_EINVAL, "null handle");
+    if (!b || !s) return fail(FPV_EINVAL, "null argument");
+    if (h->mode != FPV_MODE_DRONE) return fail(FPV_EINVAL, "point and shoot is the Drone's guidance law: not for a Racer handle");
+    if (h->K.flags & FPV_FLAG_FP16_STATE)
+        return fail(FPV_EINVAL, "point and shoot cannot read fp16 state (FPV_FLAG_FP16_STATE): a reader of the packed quaternion is the follow-up");
+    if (!b->state) return fail(FPV_EINVAL, "fpv_buffers_t.state is null");
+    if (b->ld < h->n) return fail(FPV_EALIGN, "fpv_buffers_t.ld is smaller than the number of drones");
+    FpvPnsArgs A;
+    const int rc = pns_args(s, h->n, &A);
+    if (rc != FPV_OK) return rc;
+    A.state = b->state; A.ld = b->ld;
+    const DeviceGuard dev(h->device);
+    if (dev.rc != FPV_OK) return dev.rc;
+    void* arg = &A;
+    return launch_args("point and shoot kernel launch", fpv_pns_kernel_fn(s->pixel != nullptr), blocks_for(h->n, kStepBlock), dim3(kStepBlock), (hipStream_t)stream, &arg);
+}
+
+int fpv_pns_eval(const fpv_pns_t* s, int64_t n, const float* p, const float* v, const float* q)
+{
+    if (fpv_pns_eval_host == nullptr) return fail(FPV_EINVAL, kPnsAbsent);
+    if (!v) return fail(FPV_EINVAL, "null argument");
+    int rc = check_eval_args(s, n, p, q);
+    if (rc != FPV_OK) return rc;
+    FpvPnsArgs A;
+    rc = pns_args(s, n, &A);
+    if (rc != FPV_OK) return rc;
+    fpv_pns_eval_host(&A, p, v, q);
     return FPV_OK;
 }
 

@@ -440,8 +440,9 @@ class _Batch(_Handle):
     # -- checkpoint / resume (the reference has none; state is just tensors here) ------------------
     _CKPT_TENSORS = ("state", "state_h", "reward", "done", "ep_return", "ep_length", "last_return",
                      "last_length", "noise_state", "pos_comp", "reset_pose", "physics", "gate_word", "gate_start", "gate_desc",
-                     "target_rows", "pursuit_pid_rows")
-    _CKPT_ROW_TENSORS = ("state", "noise_state", "pos_comp", "reset_pose", "physics", "target_rows", "pursuit_pid_rows")        # [rows, ld]: stored as their logical columns [rows, num_envs]
+                     "target_rows", "pursuit_pid_rows", "pns_pid_rows", "pns_prev_pixel", "pns_target_rows")
+    _CKPT_ROW_TENSORS = ("state", "noise_state", "pos_comp", "reset_pose", "physics", "target_rows", "pursuit_pid_rows", "pns_pid_rows",
+                         "pns_prev_pixel", "pns_target_rows")        # [rows, ld]: stored as their logical columns [rows, num_envs]
 
     def _state_h_views(self, t: Optional[torch.Tensor] = None, ld: Optional[int] = None):
         """(pair rows [5, ld, 2], thrust row [ld]) int16 views of an fp16 storage tensor laid out with row stride `ld`"""
@@ -793,8 +794,8 @@ class _Batch(_Handle):
     def set_chase_camera(self, camera=None, max_depth: float = 15.0) -> None:
         """The camera the target chase looks through - a fpyv_amd.camera.DepthCamera / Camera; None: the params' `camera` section,
         the reference's 640 x 480 - and the reach within which it sees the target (simulator.py:102: 15).  Takes effect with the
-        next `calculate_needed_force_orientation` / `track`."""
-        self._chase_camera, self._chase_structs = (camera, float(max_depth)), {}
+        next `calculate_needed_force_orientation` / `track` / `point_and_shoot`."""
+        self._chase_camera, self._chase_structs, self._pns_structs = (camera, float(max_depth)), {}, {}
 
     def _chase(self, pixel, target, ref_frame: str, mode: str, rows: torch.Tensor):
         """One launch of fpv_chase_guide on torch's current stream into the preallocated outputs"""
@@ -853,6 +854,130 @@ class _Batch(_Handle):
             self._chase_track_rows = torch.zeros((_lib.FPV_PID_ROWS, self.ld), dtype=torch.float32, device=self.device)
         _, _, pix, vis = self._chase(None, target, "world", "level", self._chase_track_rows)
         return pix, vis
+
+    # -- point and shoot ---------------------------------------------------------------------------
+    pns_prev_pixel: Optional[torch.Tensor] = None     # [2, ld] Drone.prev_pixel of every drone (NaN = None), made by the law's first use
+
+    @property
+    def pns_pid_rows(self) -> Optional[torch.Tensor]:
+        """The [4, ld] guidance-PID rows point and shoot advances (None before its first use): a checkpoint's rows"""
+        return None if self.pns_prev_pixel is None else self._chase_rows()
+
+    @property
+    def pns_target_rows(self) -> Optional[torch.Tensor]:
+        """The pursuit task's [3, ld] target positions where point and shoot is in use (else None): an env with assist= reads them
+        BEFORE the step's pursuit call writes them again, so a checkpoint has to carry them"""
+        return None if self.pns_prev_pixel is None else self.target_position_rows
+
+    def _pns_rows(self) -> torch.Tensor:
+        if self.pns_prev_pixel is None:
+            self.pns_prev_pixel = torch.full((2, self.ld), float("nan"), dtype=torch.float32, device=self.device)
+            f32 = dict(dtype=torch.float32, device=self.device)
+            u8 = dict(dtype=torch.uint8, device=self.device)
+            self._pns_out = dict(rotation=torch.zeros((self.n, 3, 3), **f32), thrust=torch.full((self.n,), float("nan"), **f32),
+                                 pixel_velocity=torch.zeros((self.n, 2), **f32), limited=torch.zeros(self.n, **u8),
+                                 visible=torch.zeros(self.n, **u8), throttle=torch.zeros(self.n, **f32))
+        return self.pns_prev_pixel
+
+    def _pns_struct(self, ref_frame: str, mode: str) -> "_lib.FpvPns":
+        from .pns import PointAndShoot
+        if getattr(self, "_chase_camera", None) is None:
+            self.set_chase_camera()
+        key = (ref_frame, mode)
+        if key not in self._pns_structs:
+            camera, max_depth = self._chase_camera
+            self._pns_structs[key] = PointAndShoot(self.params, camera=camera, ref_frame=ref_frame, mode=mode, max_depth=max_depth).derive()
+        return self._pns_structs[key]
+
+    def _pns_launch(self, s: "_lib.FpvPns", pixel, action, target, restart) -> None:
+        """One launch of fpv_pns_guide on torch's current stream into the preallocated outputs: `pixel` None | [n, 2] tensor, `action`
+        None | [n, 4] tensor, `target` None | host float32 [3] array | [3, >= n] device rows, `restart` None | [n] uint8 tensor"""
+        prev, rows = self._pns_rows(), self._chase_rows()
+        out = self._pns_out
+        s.pid_state, s.pid_ld, s.prev_pixel, s.prev_pixel_ld = rows.data_ptr(), rows.shape[1], prev.data_ptr(), prev.shape[1]
+        s.pixel = pixel.data_ptr() if pixel is not None else None
+        s.action = action.data_ptr() if action is not None else None
+        s.restart = restart.data_ptr() if restart is not None else None
+        s.target = s.target_rows = None
+        if isinstance(target, np.ndarray):
+            s.target = target.ctypes.data
+        elif target is not None:
+            s.target_rows, s.target_ld = target.data_ptr(), target.stride(0)
+        s.rotation, s.thrust, s.pixel_velocity = out["rotation"].data_ptr(), out["thrust"].data_ptr(), out["pixel_velocity"].data_ptr()
+        s.limited, s.visible, s.throttle = out["limited"].data_ptr(), out["visible"].data_ptr(), out["throttle"].data_ptr()
+        self._sensor_raw(self._L.fpv_pns_guide, s, None)
+        self._pns_keep = (pixel, action, target, restart)
+
+    def _per_drone(self, x, width: int, what: str) -> torch.Tensor:
+        """[width] or [num_envs, width] -> contiguous float32 [num_envs, width] on the device"""
+        t = torch.as_tensor(np.asarray(x, dtype=np.float32) if not torch.is_tensor(x) else x, dtype=torch.float32, device=self.device)
+        if t.shape == (width,):
+            t = t.expand(self.n, width)
+        if t.shape != (self.n, width):
+            raise ValueError(f"{what} must be [{width}] or [{self.n}, {width}], got {tuple(t.shape)}")
+        return t.contiguous()
+
+    def point_and_shoot(self, pixel, action, ref_frame: str = "world", mode: str = "level", target=None, restart=None):
+        """Drone.point_and_shoot (components.py:312-381) for every drone, one kernel (include/fpv_abi.h "Point and shoot"): `pixel`
+        [num_envs, 2] (x, y) where the drone's camera sees its target, or None = find it: then `target` is a Target or a centre [3]
+        for all drones, or [3, >= num_envs] device rows with a centre per drone (`target_position_rows` of a pursuit task as they
+        are).  `action` [4] or [num_envs, 4]: action[1] where on the image the target is to be held, action[2:] the virtual offset
+        of the target in half-images (action[0] is not used: the reference discards what it feeds); None = zeros.  Returns
+        (rotation_matrix [num_envs, 3, 3], thrust_force [num_envs]) in preallocated tensors that the next call overwrites - what
+        `step(..., rotation_matrix=, thrust_force=)` takes as they are; `pixel_velocity`, `thrust_limited` and `pns_throttle` hold
+        the call's other outputs.  A drone that does not see the target, or whose action is not finite, gets thrust_force NaN
+        (step: not overridden) and an identity matrix.  The reference's thrust-limit loop is taken in closed form.
+        Uses and advances `force_multiplier_pid`'s state and `pns_prev_pixel` for the drones it guides; `restart` [num_envs]
+        flags drones that reset both first; `reset(mask)` clears them."""
+        if ref_frame not in _lib.CHASE_FRAMES:
+            raise ValueError("Unknown reference frame")                          # components.py:343
+        if mode not in _lib.CHASE_MODES:
+            raise ValueError("Unknown mode")                                     # components.py:377
+        pix = None if pixel is None else self._per_drone(pixel, 2, "pixel")
+        act = None if action is None else self._per_drone(action, 4, "action")
+        tgt = None
+        if target is not None:
+            if torch.is_tensor(target) and target.dim() == 2:
+                if target.shape[0] != 3 or target.shape[1] < self.n or target.stride(1) != 1 or target.dtype != torch.float32 or target.device != self._dev:
+                    raise ValueError(f"target rows must be a float32 [3, >= {self.n}] tensor on {self.device} with unit column stride")
+                tgt = target
+            else:
+                c = target.position if hasattr(target, "position") else target
+                tgt = np.ascontiguousarray(np.asarray(c.cpu() if torch.is_tensor(c) else c, dtype=np.float32).reshape(3))
+        elif pix is None:
+            raise ValueError("pixel=None needs target=: a Target, a centre [3] or [3, num_envs] rows")
+        rs = None
+        if restart is not None:
+            rs = torch.as_tensor(restart, device=self.device).to(torch.uint8).contiguous()
+            if rs.shape != (self.n,):
+                raise ValueError("restart must have shape (num_envs,)")
+        self._pns_launch(self._pns_struct(ref_frame, mode), pix, act, tgt, rs)
+        return self._pns_out["rotation"], self._pns_out["thrust"]
+
+    @property
+    def pixel_velocity(self) -> Optional[torch.Tensor]:
+        """[num_envs, 2] Drone.pixel_velocity after the last `point_and_shoot`, pixels per second (NaN where the drone was not guided)"""
+        return None if self.pns_prev_pixel is None else self._pns_out["pixel_velocity"]
+
+    @property
+    def thrust_limited(self) -> Optional[torch.Tensor]:
+        """[num_envs] uint8 of the last `point_and_shoot`: 0 not limited, 1 thrust limit reached, 2 limit out of reach"""
+        return None if self.pns_prev_pixel is None else self._pns_out["limited"]
+
+    @property
+    def pns_throttle(self) -> Optional[torch.Tensor]:
+        """[num_envs] thrust2throttle(thrust_force) of the last `point_and_shoot`, in [-1, 1]"""
+        return None if self.pns_prev_pixel is None else self._pns_out["throttle"]
+
+    def _pns_reset(self, mask) -> None:
+        """Drone.reset (components.py:166-168) for the law's rows: prev_pixel = None for the drones of `mask` (None = all)"""
+        if self.pns_prev_pixel is None:
+            return
+        if mask is None:
+            self.pns_prev_pixel.fill_(float("nan"))
+        else:
+            m = torch.as_tensor(mask, device=self.device).bool()
+            self.pns_prev_pixel[:, :self.n].masked_fill_(m, float("nan"))
 
     def set_done_bits_target(self, target: Any = None, stride_words: int = 0) -> None:
         """Where the kernel writes the bit-packed done mask (one wave ballot per 64 drones):
@@ -1168,6 +1293,7 @@ class DroneBatch(_Batch):
         self._reset_raw(mask=mask, position=position, velocity=velocity, ypr=ypr)
         if self._force_multiplier_pid is not None:
             self._force_multiplier_pid.reset(mask)                  # components.py:166
+        self._pns_reset(mask)                                       # components.py:167-168
 
     def step(self, action, wind_velocity_vector=None, object_list=(), rotation_matrix=None, thrust_force=None,
              return_imu: bool = True):
@@ -1315,7 +1441,7 @@ class FpvVecEnv:
     def __init__(self, params: Optional[DroneParams] = None, num_envs: int = 1, device: Any = "cuda:0",
                  mode: str = "drone", auto_reset: bool = True, track_episodes: bool = True,
                  wind: Sequence[float] = (0.0, 0.0, 0.0), object_list=(), partitions: int = 1, depth_every: int = 1,
-                 guided: bool = False, **batch_options: Any):
+                 guided: bool = False, assist: Any = None, assist_sticks: Sequence[float] = (0.0, 0.0, 0.0, 0.0), **batch_options: Any):
         """`batch_options` go to DroneBatch / RacerBatch (stick_noise=, noise_seed=, drone_id_offset=,
         fp16_state=, with_obs_aos=, kahan_position=, with_done_bits=, per_drone_physics=, ...); `object_list` is the
         collision world of every step (fpyv_amd.objects); `partitions` > 1 enables step_async / step_wait.  `range_rays=`
@@ -1329,7 +1455,20 @@ class FpvVecEnv:
         step are followed by the pursuit call on the same stream (before the scan and the render), which adds the task's payment
         to `reward` and the episode return; `target_obs` [num_envs, 7], `target_position`, `target_event`, `captures` and
         info["target_obs" | "target_event" | "captures"] hold the result.  With `PursuitTask(guide=...)`, `guided=True` flies
-        every step under the override the previous call wrote (`batch.pursuit_guidance`): the reference's chase loop."""
+        every step under the override the previous call wrote (`batch.pursuit_guidance`): the reference's chase loop.
+        `assist=` (a fpyv_amd.pns.PointAndShoot, with `pursuit=`) makes the four commands of point and shoot the env's action:
+        `step(action [num_envs, 4])` runs the law against `target_position` as the last pursuit call left it, flies the step under
+        that override with the sticks `assist_sticks`, then makes the pursuit call as ever; a lane that was reset - by mask or in
+        the kernel - restarts its guidance PID and prev_pixel.  Not with guided=True; not with partitions > 1 (not built)."""
+        if assist is not None:
+            if batch_options.get("pursuit") is None:
+                raise ValueError("assist= needs pursuit=: the law steers every drone toward its own target")
+            if guided:
+                raise ValueError("assist= and guided=True both write the step's override: choose one")
+            if int(partitions) > 1:
+                raise ValueError("assist= with partitions > 1 is not built: the law runs on the whole population's stream")
+            if mode != "drone":
+                raise ValueError("assist= is the Drone's guidance law: not for a Racer")
         if mode not in ("drone", "racer"):
             raise ValueError(f'mode must be "drone" or "racer", got {mode!r}')
         params = params if params is not None else load_params(fps=1000)
@@ -1366,6 +1505,15 @@ class FpvVecEnv:
                 # for the single chain at 2^20 drones - split phase is for closed loops, where the policy is what gets hidden)
                 self._part_views = [None] * len(self._parts)
         self.partitions = max(1, len(self._parts))
+        self.assist = assist
+        if assist is not None:
+            b = self.batch
+            self._assist_struct = assist.derive()
+            b._pns_rows()
+            b.force_multiplier_pid                      # the rows the law advances exist from the start: a checkpoint holds them
+            self._assist_sticks = torch.tensor([float(x) for x in assist_sticks], dtype=torch.float32, device=b.device).expand(b.n, 4).contiguous()
+            # every step reads the override the law just wrote
+            b._buf.rotation_override, b._buf.thrust_override = b._pns_out["rotation"].data_ptr(), b._pns_out["thrust"].data_ptr()
         self.guided = bool(guided)
         if self.guided:
             g = getattr(self.batch, "pursuit_guidance", None)
@@ -1531,6 +1679,12 @@ class FpvVecEnv:
                 self.step_wait(k)
             return self.obs, self.batch.reward, self.batch.done, self._info(self.batch, 0, self.num_envs)
         self._bind_world(self.batch)
+        if self.assist is not None:
+            b = self.batch
+            # the law against every drone's target as the last pursuit call left it; a lane the last step reset in the kernel restarts
+            b._pns_launch(self._assist_struct, None, b._per_drone(action, 4, "action"), b.target_position_rows,
+                          b.done_u8 if b._auto_reset else None)
+            action = self._assist_sticks
         self.batch._step_raw(action)
         self._sense_after_step(self.batch)
         return self.obs, self.batch.reward, self.batch.done, self._info(self.batch, 0, self.num_envs)

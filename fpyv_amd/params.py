@@ -174,6 +174,15 @@ class DroneParams:
         """total thrust [N] -> throttle stick, clipped to [-1, 1] (components.py:137)."""
         return np.clip(np.polyval(self.inverse_thrust_poly, thrust) / 100.0 * 2.0 - 1.0, -1.0, 1.0)
 
+    @property
+    def thrust2throttle_poly(self) -> np.ndarray:
+        """the cubic of `model_xy(thrust, throttle)` (components.py:137), highest power first: throttle percent of a thrust [N]"""
+        return self.inverse_thrust_poly
+
+    def thrust2throttle(self, force: Any) -> Any:
+        """Drone.thrust2throttle (components.py:137): thrust [N] -> throttle in [-1, 1], clipped"""
+        return self.stick_from_thrust(force)
+
     def replace(self, **kw) -> "DroneParams":
         return dataclasses.replace(copy.deepcopy(self), **kw)
 

@@ -314,7 +314,8 @@ typedef struct fpv_env* fpv_handle_t;
 
 int fpv_abi_version(void);
 /* sizeof of the ABI structs as this library was compiled (0 fpv_params_t, 1 fpv_buffers_t, 2 fpv_objects_t,
- * 3 fpv_pid_params_t, 4 fpv_cache_model_t, 5 fpv_gate_course_t, 6 fpv_range_scan_t, 7 fpv_depth_render_t, 8 fpv_chase_t):
+ * 3 fpv_pid_params_t, 4 fpv_cache_model_t, 5 fpv_gate_course_t, 6 fpv_range_scan_t, 7 fpv_depth_render_t, 8 fpv_chase_t,
+ * 10 fpv_pursuit_t, 12 fpv_pns_t):
  * lets a foreign-language binding verify its struct declarations at load time */
 int fpv_sizeof(int which);
 /* rows of the state matrix for a mode (FPV_DRONE_ROWS / FPV_RACER_ROWS), or FPV_EINVAL */
@@ -836,6 +837,72 @@ int fpv_pursuit_reset(fpv_handle_t h, const fpv_buffers_t* b, const fpv_pursuit_
  * be NULL); reset != 0: the reset call.  Every pointer of *s is HOST memory. */
 int fpv_pursuit_eval(const fpv_pursuit_t* s, int64_t n, uint64_t drone_id_offset, const float* p /*[n][3]*/, const float* v /*[n][3]*/,
                      const float* q /*[n][4] wxyz*/, const uint8_t* done_or_mask, float* reward, int reset);
+
+/* ---- Point and shoot: the reference's steered guidance law for N drones (functions and one struct only - FPV_ABI_VERSION,
+ * fpv_params_t and fpv_buffers_t are those of ABI 9) ---------------------------------------------------------------------------------
+ * Drone.point_and_shoot(pixel, action, ref_frame, mode) (components.py:312-381): the target chase's sibling whose four commands
+ * steer it - action[1] is where on the image (vertical axis, -1..1) the target is to be held, action[2:] a virtual offset of the
+ * target in half-images; action[0] only feeds a yaw angle the reference discards and is not used.  One kernel, a lane per drone,
+ * reads p, v and q of an fp32 drone handle, the drone's four guidance-PID rows (the rows the chase uses: the reference has one PID for
+ * both laws) and its two prev_pixel rows, writes rotation[n][9] and thrust[n] in the layout fpv_buffers_t.rotation_override /
+ * thrust_override take.  csrc/fpv_pns.h restates the law as computed and is the ONE definition the kernel (csrc/fpv_pns.hip) and
+ * fpv_pns_eval run: the same bits.
+ *   pixel: the caller's (x, y) per drone, or - pixel == NULL - the projection of the centre of `target` (one for all, HOST [3]) or of
+ *     target_rows[3][target_ld] (one per drone, the layout fpv_pursuit_t.position writes), seen as the chase sees it.  A drone that
+ *     does not see the target, whose given pixel is NaN or whose action is not finite is not guided: thrust = NaN, rotation =
+ *     identity, visible = 0, pixel_velocity = throttle = NaN, limited = 0, PID rows and prev_pixel untouched.
+ *   thrust limit: the reference's `while |F| > max_throttle_in_force` loop (:358-366) in closed form, no loop: the multiplier becomes
+ *     clip(-b + sqrt(b^2 - |B|^2 + Fmax^2), min_output, max_output), b = d . B; where even min_output gives |F| > Fmax (the
+ *     reference never returns) the direction of that F with thrust = Fmax.  limited: 0 not limited, 1 limited, 2 out of reach.
+ *   prev_pixel[2][prev_pixel_ld]: the law's pixel of the previous call; NaN = the reference's None (the first call: velocity 0).
+ *   restart[n]: a lane whose byte is set first resets its PID rows (PID.reset) and its prev_pixel (Drone.reset).
+ *   defined where the reference gives NaN as the chase defines it.
+ * It moves 156 bytes per drone with per-drone targets and commands (10 state floats, 4 PID and 2 prev_pixel rows, 3 target floats and
+ * 4 commands read; 4 PID and 2 prev_pixel rows and 10 floats written), 171 with the restart bytes and every optional output. */
+typedef struct fpv_pns {
+    uint32_t struct_size;            /* sizeof(fpv_pns_t) = fpv_sizeof(12) (11 stays "no such struct") */
+    int32_t  width, height;          /* the camera numbers fpv_chase_derive writes: copy them from its fpv_chase_t (fpv_pns_derive does) */
+    int32_t  ref_frame;              /* FPV_CHASE_WORLD / FPV_CHASE_DRONE */
+    int32_t  mode;                   /* FPV_CHASE_LEVEL / FPV_CHASE_FRONTARGET */
+    int32_t  _reserved;
+    double   focal_length;
+    double   relative_rotation[9];
+    double   relative_position[3];
+    double   max_depth;              /* finite, > 0 */
+    double   mass;                   /* kg: g = (0, 0, -9.81 mass) */
+    double   virtual_drag_coefficient, virtual_lift_coefficient, tof_effective_distance;   /* params.yaml point_and_shoot */
+    double   max_throttle_in_force;  /* Fmax > 0, newtons */
+    double   thrust2throttle_poly[4];/* throttle percent as a cubic of the thrust, highest power first (components.py:137) */
+    fpv_pid_params_t pid;            /* Drone.force_multiplier_pid (components.py:143-145) */
+    float*   pid_state;              /* [FPV_PID_ROWS][pid_ld], read and written; DEVICE for fpv_pns_guide, HOST for fpv_pns_eval (as every */
+    int64_t  pid_ld;                 /* >= n                                                pointer below but `target`); 4-byte aligned */
+    float*   prev_pixel;             /* [2][prev_pixel_ld], read and written */
+    int64_t  prev_pixel_ld;          /* >= n */
+    const float* pixel;              /* [n][2] (x, y) or NULL = find the target; 8-byte aligned */
+    const float* target;             /* HOST [3], read during the call: one target centre for all, or NULL */
+    const float* target_rows;        /* [3][target_ld]: a target centre per drone, or NULL.  pixel == NULL needs exactly one of the two */
+    int64_t  target_ld;              /* >= n */
+    const float* action;             /* [n][4] or NULL = zeros; 16-byte aligned */
+    const uint8_t* restart;          /* [n] or NULL */
+    float*   rotation;               /* [n][9] row-major body -> world, 4-byte aligned */
+    float*   thrust;                 /* [n] newtons; NaN = not guided */
+    float*   pixel_velocity;         /* [n][2] or NULL: Drone.pixel_velocity, pixels per second; 8-byte aligned */
+    uint8_t* limited;                /* [n] or NULL: 0, 1 or 2 */
+    uint8_t* visible;                /* [n] or NULL: exactly 0 or 1 */
+    float*   throttle;               /* [n] or NULL: thrust2throttle(thrust) in [-1, 1] */
+} fpv_pns_t;
+/* Fills width, height, focal_length, relative_rotation and relative_position of *out with what fpv_chase_derive computes for the
+ * camera (host arithmetic only; every other field is left alone); refuses what fpv_chase_derive refuses. */
+int fpv_pns_derive(const fpv_camera_t* camera, fpv_pns_t* out);
+/* One call of the law for the handle's n drones at b->state / b->ld on `stream`, under the handle's device: allocates nothing,
+ * never synchronises, does not advance the step index and does not touch the rotation.  FPV_EINVAL / FPV_EALIGN / FPV_EPARAM, by
+ * name: everything fpv_chase_guide refuses of the fields the two structs share, max_throttle_in_force not positive, a polynomial
+ * that is not finite, null prev_pixel, prev_pixel_ld or target_ld < n, both `target` and `target_rows` given, neither given without
+ * a pixel, misaligned pointers; and in a library built without csrc/fpv_pns.hip. */
+int fpv_pns_guide(fpv_handle_t h, const fpv_buffers_t* b, const fpv_pns_t* s, void* stream);
+/* The kernel's own lane function on the host (no handle, no device): drone i of n at p[i][3] with velocity v[i][3] and attitude
+ * q[i][4] (wxyz); every pointer of *s is HOST memory. */
+int fpv_pns_eval(const fpv_pns_t* s, int64_t n, const float* p /*[n][3]*/, const float* v /*[n][3]*/, const float* q /*[n][4] wxyz*/);
 
 const char* fpv_last_error(void);
 const char* fpv_error_name(int code);
