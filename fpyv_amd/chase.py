@@ -93,7 +93,7 @@ class ChaseGuidance:
             st = np.zeros((_lib.FPV_PID_ROWS, n), dtype=np.float32)
             st[3] = 1.0
         else:
-            st = np.array(pid_state, dtype=np.float32).reshape(_lib.FPV_PID_ROWS, n)
+            st = np.array(pid_state, dtype=np.float32, order="C").reshape(_lib.FPV_PID_ROWS, n)      # a[:, idx] is column-major
         s = self.derive(target)
         rot, thrust = np.zeros((n, 9), dtype=np.float32), np.zeros(n, dtype=np.float32)
         pix_out, vis = _aligned8(n), np.zeros(n, dtype=np.uint8)

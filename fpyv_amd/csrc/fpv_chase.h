@@ -32,8 +32,10 @@
 //        angle below 1e-6, where an fp32 cross product holds no direction): b is REPLACED by the world x axis (1, 0, 0), and when F
 //        is parallel to that too (same test) by the world y axis (0, 1, 0).  The columns are then x, y, F of the same formulas.
 //      F = 0 (|F|^2 below 2^-96): rotation = identity, thrust_force = 0.
-//      anything of the result not finite (an overflow of a finite but absurd state): the lane is not guided, as in 1.
-//    So no finite state gives a NaN matrix.
+//      anything of the result not finite (an overflow of a finite but absurd state): the lane is not guided, as in 1.  The two
+//        column norms |x| and |y| count as results: a norm that overflows to +inf where its column is still finite (|F| about
+//        1e19 N) would otherwise divide that column to zero - a finite matrix that is no rotation.
+//    So no finite state gives a NaN matrix, and every guided lane's matrix is orthonormal.
 #pragma once
 
 #include <math.h>
@@ -143,7 +145,7 @@ FPV_HD void fpv_chase_lane_at(const FpvChaseK& K, float tcx, float tcy, float tc
     o.rot[0] = zero ? 1.0f : xx / xnrm; o.rot[1] = zero ? 0.0f : yx / ynrm; o.rot[2] = zero ? 0.0f : Fx / fn;
     o.rot[3] = zero ? 0.0f : xy / xnrm; o.rot[4] = zero ? 1.0f : yy / ynrm; o.rot[5] = zero ? 0.0f : Fy / fn;
     o.rot[6] = zero ? 0.0f : xz / xnrm; o.rot[7] = zero ? 0.0f : yz / ynrm; o.rot[8] = zero ? 1.0f : Fz / fn;
-    bool fin = fpv_chase_finite(fn);
+    bool fin = fpv_chase_finite(fn) && fpv_chase_finite(xnrm) && fpv_chase_finite(ynrm);
     for (int j = 0; j < 9; ++j) fin = fin && fpv_chase_finite(o.rot[j]);
     o.seen = seen;
     o.guided = seen && fin;

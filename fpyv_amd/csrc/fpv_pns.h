@@ -166,7 +166,7 @@ FPV_HD void fpv_pns_lane(const FpvPnsK& P, float tcx, float tcy, float tcz, floa
     o.rot[0] = zero ? 1.0f : xx / xnrm; o.rot[1] = zero ? 0.0f : yx / ynrm; o.rot[2] = zero ? 0.0f : Fx / fn;
     o.rot[3] = zero ? 0.0f : xy / xnrm; o.rot[4] = zero ? 1.0f : yy / ynrm; o.rot[5] = zero ? 0.0f : Fy / fn;
     o.rot[6] = zero ? 0.0f : xz / xnrm; o.rot[7] = zero ? 0.0f : yz / ynrm; o.rot[8] = zero ? 1.0f : Fz / fn;
-    bool fin = fpv_chase_finite(fn) && fpv_chase_finite(velx) && fpv_chase_finite(vely);
+    bool fin = fpv_chase_finite(fn) && fpv_chase_finite(xnrm) && fpv_chase_finite(ynrm) && fpv_chase_finite(velx) && fpv_chase_finite(vely);
     for (int j = 0; j < 9; ++j) fin = fin && fpv_chase_finite(o.rot[j]);
     o.seen = seen;
     o.guided = seen && fin;

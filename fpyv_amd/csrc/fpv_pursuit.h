@@ -31,7 +31,8 @@
 //      (fpv_math.h), the physics sample's is (.., "PHYS", 0): word 3 = "TRGT" = 0x54475254 meets the jitter's only at step index
 //      >= 0x54475254 * 2^32 (6e18 steps) and the sample's never, so the streams are disjoint under one seed too.
 //      After a respawn everything below sees the NEW target (standing at its index j, velocity zero).
-//   6. observe: R^T w, R^T (v_target - v), dist    7. hand the payment to reward[i] / ep_return[i] (never on a rebasing lane, whose
+//   6. observe: R^T w, R^T (v_target - v), dist; the target keeps its height, and the third component of the difference is formed
+//      as the negation -v.z (-0 for v.z = +0)    7. hand the payment to reward[i] / ep_return[i] (never on a rebasing lane, whose
 //      last_return the step kernel has just written)    8. GUIDE: the guidance law of fpv_chase.h against THIS target.
 #pragma once
 
@@ -111,7 +112,7 @@ FPV_HD void fpv_pursuit_task(const FpvPursuitK& P, const float* circle, uint32_t
     // ---- 1. advance
     const bool fresh = (T.count & FPV_TGT_FRESH) != 0u;
     float tx = fmaf(T.path_r, ax, T.cx), ty = fmaf(T.path_r, ay, T.cy), tz = T.cz;
-    float ux = 0.0f, uy = 0.0f, uz = 0.0f;                      // the target's velocity
+    float ux = 0.0f, uy = 0.0f;                                 // the target's velocity: it keeps its height
     if (P.advance) {
         if (!fresh) {
             ux = (tx - fmaf(T.path_r, bx, T.cx)) / P.dt;
@@ -149,7 +150,8 @@ FPV_HD void fpv_pursuit_task(const FpvPursuitK& P, const float* circle, uint32_t
     T.prev_dist = dist;
     // ---- 6. observe
     const FpvRot R = fpv_rot(q);
-    const float rx = ux - vx, ry = uy - vy, rz = uz - vz;
+    // (6. above: the negation, not the difference 0 - v.z, which is +0 for v.z = +0)
+    const float rx = ux - vx, ry = uy - vy, rz = -vz;
     o.obs[0] = fmaf(R.r00, wx, fmaf(R.r10, wy, R.r20 * wz));
     o.obs[1] = fmaf(R.r01, wx, fmaf(R.r11, wy, R.r21 * wz));
     o.obs[2] = fmaf(R.r02, wx, fmaf(R.r12, wy, R.r22 * wz));

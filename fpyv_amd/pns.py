@@ -58,8 +58,8 @@ class PointAndShoot(ChaseGuidance):
             st = np.zeros((_lib.FPV_PID_ROWS, n), dtype=np.float32)
             st[3] = 1.0
         else:
-            st = np.array(pid_state, dtype=np.float32).reshape(_lib.FPV_PID_ROWS, n)
-        prev = np.full((2, n), np.nan, dtype=np.float32) if prev_pixel is None else np.array(prev_pixel, dtype=np.float32).reshape(2, n)
+            st = np.array(pid_state, dtype=np.float32, order="C").reshape(_lib.FPV_PID_ROWS, n)
+        prev = np.full((2, n), np.nan, dtype=np.float32) if prev_pixel is None else np.array(prev_pixel, dtype=np.float32, order="C").reshape(2, n)
         s = self.derive()
         keep = []
         if pixel is not None:

@@ -183,7 +183,7 @@ class PursuitTask:
                 st = np.zeros((_lib.FPV_PID_ROWS, n), dtype=np.float32)
                 st[_lib_pid_first()] = 1.0
             else:
-                st = np.array(pid_state, dtype=np.float32).reshape(_lib.FPV_PID_ROWS, n)
+                st = np.array(pid_state, dtype=np.float32, order="C").reshape(_lib.FPV_PID_ROWS, n)
             rot, thrust, pix, vis = np.zeros((n, 9), dtype=np.float32), np.zeros(n, dtype=np.float32), _aligned8(n), np.zeros(n, dtype=np.uint8)
             g.pid_state, g.pid_ld, g.rotation, g.thrust = st.ctypes.data, n, rot.ctypes.data, thrust.ctypes.data
             g.pixel_out, g.visible = pix.ctypes.data, vis.ctypes.data
