@@ -63,7 +63,8 @@ EXPORTS = ("fpv_abi_version", "fpv_sizeof", "fpv_state_rows", "fpv_algorithmic_b
            "fpv_camera_derive", "fpv_depth_render", "fpv_depth_eval",
            "fpv_chase_derive", "fpv_chase_guide", "fpv_chase_eval",
            "fpv_pursuit_derive", "fpv_pursuit_sample", "fpv_pursuit_step", "fpv_pursuit_reset", "fpv_pursuit_eval",
-           "fpv_pns_derive", "fpv_pns_guide", "fpv_pns_eval")
+           "fpv_pns_derive", "fpv_pns_guide", "fpv_pns_eval",
+           "fpv_boxes_derive", "fpv_detect_derive", "fpv_detect_boxes", "fpv_detect_eval")
 
 
 class FpvParams(C.Structure):
@@ -301,6 +302,25 @@ class FpvPns(C.Structure):
                 ("pixel_velocity", C.c_void_p), ("limited", C.c_void_p), ("visible", C.c_void_p), ("throttle", C.c_void_p)]
 
 
+FPV_MAX_BOXES = FPV_MAX_OBJECTS + FPV_MAX_GATES      # fpv_detect_boxes: the objects of a list, the gates of a course (fpv_abi.h "Object detections")
+DETECT_PIXELS = {"int": 0, "float": 1}
+
+
+class FpvBoxes(C.Structure):
+    """fpv_boxes_t: the box table fpv_boxes_derive writes - (min x, y, z, max x, y, z) per slot."""
+    _fields_ = [("count", C.c_int32), ("box", (C.c_float * 6) * FPV_MAX_BOXES)]
+
+
+class FpvDetect(C.Structure):
+    """fpv_detect_t: the camera numbers fpv_detect_derive computes, the pixel mode and the clip flag, the box table (host memory),
+    the optional per-drone target rows and radii, and the three outputs (device for fpv_detect_boxes, host for fpv_detect_eval)."""
+    _fields_ = [("struct_size", C.c_uint32), ("width", C.c_int32), ("height", C.c_int32), ("pixel_mode", C.c_int32), ("clip", C.c_int32),
+                ("_reserved", C.c_int32), ("focal_length", C.c_double), ("relative_rotation", C.c_double * 9),
+                ("relative_position", C.c_double * 3), ("table", C.c_void_p), ("target_rows", C.c_void_p), ("target_ld", C.c_int64),
+                ("target_radius", C.c_void_p), ("target_radius_all", C.c_float), ("_reserved2", C.c_float), ("boxes", C.c_void_p),
+                ("box_depth", C.c_void_p), ("box_visible", C.c_void_p), ("ld", C.c_int64)]
+
+
 class FpvPursuit(C.Structure):
     """fpv_pursuit_t: the path table, the rewards, the spawn box and the flags of a pursuit call, the target rows and the optional
     outputs (device for fpv_pursuit_step / _reset, host for fpv_pursuit_eval), and the optional guidance law (a fpv_chase_t)."""
@@ -416,11 +436,16 @@ def lib() -> C.CDLL:
     L.fpv_pns_derive.argtypes = [C.POINTER(FpvCamera), C.POINTER(FpvPns)]
     L.fpv_pns_guide.argtypes = [vp, pb, C.POINTER(FpvPns), vp]
     L.fpv_pns_eval.argtypes = [C.POINTER(FpvPns), i64, vp, vp, vp]
+    L.fpv_boxes_derive.argtypes = [vp, vp, vp, C.c_int, C.c_int, C.POINTER(FpvBoxes)]
+    L.fpv_detect_derive.argtypes = [C.POINTER(FpvCamera), C.POINTER(FpvDetect)]
+    L.fpv_detect_boxes.argtypes = [vp, pb, C.POINTER(FpvDetect), vp]
+    L.fpv_detect_eval.argtypes = [C.POINTER(FpvDetect), i64, vp, vp]
     if L.fpv_abi_version() != FPV_ABI_VERSION:
         raise ImportError(f"libfpv_hip.so ABI {L.fpv_abi_version()} != binding {FPV_ABI_VERSION} - rebuild the library "
                           "(`python -c 'import __graft_entry__ as g; g.build()'`)")
     for which, struct in ((0, FpvParams), (1, FpvBuffers), (2, FpvObjects), (3, FpvPidParams), (4, FpvCacheModel), (5, FpvGateCourse),
-                          (6, FpvRangeScan), (7, FpvDepthRender), (8, FpvChase), (10, FpvPursuit), (12, FpvPns)):
+                          (6, FpvRangeScan), (7, FpvDepthRender), (8, FpvChase), (10, FpvPursuit), (12, FpvPns), (14, FpvDetect),
+                          (16, FpvBoxes)):
         if L.fpv_sizeof(which) != C.sizeof(struct):
             raise ImportError(f"{struct.__name__}: ctypes declares {C.sizeof(struct)} bytes, libfpv_hip.so has "
                               f"{L.fpv_sizeof(which)} - _lib.py and include/fpv_abi.h are out of step")

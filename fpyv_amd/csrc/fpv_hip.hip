@@ -39,6 +39,7 @@
 #include "fpv_depth.h"
 #include "fpv_chase.h"
 #include "fpv_pns.h"
+#include "fpv_detect.h"
 #include "fpv_pursuit.h"
 
 namespace {
@@ -871,6 +872,9 @@ extern "C" __attribute__((weak, visibility("hidden"))) void fpv_chase_eval_host(
 // The kernels of csrc/fpv_pns.hip (with and without a supplied pixel) and its host loop, weak in the same way: one FpvPnsArgs.
 extern "C" __attribute__((weak, visibility("hidden"))) void* fpv_pns_kernel_fn(int pixel);
 extern "C" __attribute__((weak, visibility("hidden"))) void fpv_pns_eval_host(const FpvPnsArgs* A, const float* p, const float* v, const float* q);
+// The kernels of csrc/fpv_detect.hip (with and without the own-target slot) and its host loop, weak in the same way: one FpvDetectArgs.
+extern "C" __attribute__((weak, visibility("hidden"))) void* fpv_detect_kernel_fn(int own);
+extern "C" __attribute__((weak, visibility("hidden"))) void fpv_detect_eval_host(const FpvDetectArgs* A, const float* p, const float* q);
 // The kernels of csrc/fpv_pursuit.hip ([guidance law][reset call]) and its host loop, weak in the same way (fpv_pursuit_step, _reset
 // and _eval say so when they are absent): one FpvPursuitArgs.
 extern "C" __attribute__((weak, visibility("hidden"))) void* fpv_pursuit_kernel_fn(int guide, int reset);
@@ -1443,7 +1447,9 @@ int fpv_sizeof(int which)
         case 8: return (int)sizeof(fpv_chase_t);
         case 10: return (int)sizeof(fpv_pursuit_t);        // 9 stays refused: the tests of six features hold it to "no such struct"
         case 12: return (int)sizeof(fpv_pns_t);            // 11 stays refused like 9
-        default: return fail(FPV_EINVAL, "fpv_sizeof: 0 = fpv_params_t, 1 = fpv_buffers_t, 2 = fpv_objects_t, 3 = fpv_pid_params_t, 4 = fpv_cache_model_t, 5 = fpv_gate_course_t, 6 = fpv_range_scan_t, 7 = fpv_depth_render_t, 8 = fpv_chase_t, 10 = fpv_pursuit_t, 12 = fpv_pns_t");
+        case 14: return (int)sizeof(fpv_detect_t);         // 13 and 15 stay refused like 9
+        case 16: return (int)sizeof(fpv_boxes_t);
+        default: return fail(FPV_EINVAL, "fpv_sizeof: 0 = fpv_params_t, 1 = fpv_buffers_t, 2 = fpv_objects_t, 3 = fpv_pid_params_t, 4 = fpv_cache_model_t, 5 = fpv_gate_course_t, 6 = fpv_range_scan_t, 7 = fpv_depth_render_t, 8 = fpv_chase_t, 10 = fpv_pursuit_t, 12 = fpv_pns_t, 14 = fpv_detect_t, 16 = fpv_boxes_t");
     }
 }
 
@@ -2021,6 +2027,123 @@ int fpv_pns_eval(const fpv_pns_t* s, int64_t n, const float* p, const float* v, 
     rc = pns_args(s, n, &A);
     if (rc != FPV_OK) return rc;
     fpv_pns_eval_host(&A, p, v, q);
+    return FPV_OK;
+}
+
+int fpv_boxes_derive(const fpv_objects_t* objects, const double* ground_size, const fpv_gate_t* gates, int gate_count, int gate_resolution,
+                     fpv_boxes_t* out)
+{
+    if (!out) return fail(FPV_EINVAL, "null argument");
+    if (gate_count < 0 || (gate_count > 0 && !gates)) return fail(FPV_EINVAL, "gates is null or gate_count negative");
+    int rc = check_object_count(objects, true);
+    if (rc != FPV_OK) return rc;
+    if (gate_count > FPV_MAX_GATES || (objects ? objects->count : 0) + gate_count > FPV_MAX_BOXES)
+        return fail(FPV_EPARAM, "a box table has at most " + std::to_string(FPV_MAX_OBJECTS) + " objects and " + std::to_string(FPV_MAX_GATES) + " gates");
+    if (gate_resolution < 1 || gate_resolution > 4096) return fail(FPV_EPARAM, "gate_resolution must be 1..4096");
+    int bad = -1;
+    const char* why = "";
+    memset(out, 0, sizeof(*out));
+    rc = fpv_detect_derive_boxes(objects, ground_size, gates, gate_count, gate_resolution, out, &bad, &why);
+    return rc == FPV_OK ? FPV_OK : fail(rc, "box " + std::to_string(bad) + ": " + why);
+}
+
+int fpv_detect_derive(const fpv_camera_t* camera, fpv_detect_t* out)
+{
+    if (!camera || !out) return fail(FPV_EINVAL, "null argument");
+    fpv_chase_t c;
+    const int rc = fpv_chase_derive(camera, &c);
+    if (rc != FPV_OK) return rc;
+    out->width = c.width; out->height = c.height; out->focal_length = c.focal_length;
+    memcpy(out->relative_rotation, c.relative_rotation, sizeof c.relative_rotation);
+    memcpy(out->relative_position, c.relative_position, sizeof c.relative_position);
+    return FPV_OK;
+}
+
+namespace {
+
+const char kDetectAbsent[] = "object detections are not in this build (the library was linked without csrc/fpv_detect.hip)";
+
+// the uniform constants of a call, its box table and its buffers, checked (n: the drones the buffers must hold): FPV_OK or the error
+int detect_args(const fpv_detect_t* s, int64_t n, FpvDetectArgs* A)
+{
+    if (s->struct_size != sizeof(fpv_detect_t)) return fail(FPV_EINVAL, "fpv_detect_t.struct_size does not match this library");
+    if (s->width < 1 || s->width > FPV_CHASE_MAX_SIDE || s->height < 1 || s->height > FPV_CHASE_MAX_SIDE)
+        return fail(FPV_EPARAM, "width and height must be 1..16384 pixels (the camera numbers come from fpv_detect_derive)");
+    if (!isfinite(s->focal_length) || !(s->focal_length > 0.0)) return fail(FPV_EPARAM, "focal_length must be finite and positive (fpv_detect_derive)");
+    for (int k = 0; k < 9; ++k)
+        if (!isfinite(s->relative_rotation[k])) return fail(FPV_EPARAM, "relative_rotation is not finite");
+    for (int k = 0; k < 3; ++k)
+        if (!isfinite(s->relative_position[k])) return fail(FPV_EPARAM, "relative_position is not finite");
+    if (s->pixel_mode != FPV_DETECT_INT && s->pixel_mode != FPV_DETECT_FLOAT) return fail(FPV_EINVAL, "unknown pixel mode");
+    const int table = s->table ? s->table->count : 0;
+    const int count = table + (s->target_rows ? 1 : 0);
+    if (table < 0 || count < 1 || count > FPV_MAX_BOXES)
+        return fail(FPV_EINVAL, "count: a detection has 1.." + std::to_string(FPV_MAX_BOXES) + " boxes, not " + std::to_string(count));
+    for (int m = 0; m < table; ++m) {
+        const float* b = s->table->box[m];
+        for (int a = 0; a < 6; ++a)
+            if (!isfinite(b[a])) return fail(FPV_EPARAM, "box " + std::to_string(m) + " is not finite");
+        for (int a = 0; a < 3; ++a)
+            if (b[a] > b[3 + a]) return fail(FPV_EPARAM, "box " + std::to_string(m) + " has min > max");
+    }
+    if (!s->boxes || !s->box_depth || !s->box_visible) return fail(FPV_EINVAL, "fpv_detect_t.boxes, box_depth or box_visible is null");
+    if (((uintptr_t)s->boxes & 3) || ((uintptr_t)s->box_depth & 3)) return fail(FPV_EALIGN, "boxes and box_depth must be 4-byte aligned");
+    if (s->ld < n) return fail(FPV_EALIGN, "fpv_detect_t.ld is smaller than the number of drones");
+    if (s->ld % 4) return fail(FPV_EALIGN, "fpv_detect_t.ld must be a multiple of 4");
+    if (s->target_rows) {
+        if (((uintptr_t)s->target_rows & 3) || ((uintptr_t)s->target_radius & 3)) return fail(FPV_EALIGN, "target_rows and target_radius must be 4-byte aligned");
+        if (s->target_ld < n) return fail(FPV_EALIGN, "fpv_detect_t.target_ld is smaller than the number of drones");
+        if (!s->target_radius && (!isfinite(s->target_radius_all) || !(s->target_radius_all >= 0.0f)))
+            return fail(FPV_EPARAM, "target_radius_all must be finite and not negative");
+    }
+    memset(A, 0, sizeof(*A));
+    FpvDetectK& K = A->K;
+    for (int k = 0; k < 9; ++k) K.rr[k] = (float)s->relative_rotation[k];
+    for (int k = 0; k < 3; ++k) K.rel[k] = (float)s->relative_position[k];
+    K.f = (float)s->focal_length; K.cx = (float)(s->width / 2.0); K.cy = (float)(s->height / 2.0);
+    K.w = (float)s->width; K.h = (float)s->height;
+    K.tr = s->target_rows && !s->target_radius ? s->target_radius_all : 0.0f;
+    K.trunc = s->pixel_mode == FPV_DETECT_INT; K.clip = s->clip != 0;
+    if (table) memcpy(A->box, s->table->box, sizeof(float) * 6 * (size_t)table);
+    A->count = count; A->table_count = table;
+    A->target_rows = s->target_rows; A->target_ld = s->target_ld; A->target_radius = s->target_rows ? s->target_radius : nullptr;
+    A->boxes = s->boxes; A->depth = s->box_depth; A->visible = s->box_visible; A->out_ld = s->ld; A->n = n;
+    return FPV_OK;
+}
+
+}  // namespace
+
+int fpv_detect_boxes(fpv_handle_t h, const fpv_buffers_t* b, const fpv_detect_t* s, void* stream)
+{
+    if (fpv_detect_kernel_fn == nullptr) return fail(FPV_EINVAL, kDetectAbsent);
+    if (!s) return fail(FPV_EINVAL, "null argument");
+    FpvDetectArgs A;
+    int rc = detect_args(s, h ? h->n : 1, &A);             // the struct first: what it refuses needs no device
+    if (rc != FPV_OK) return rc;
+    if (!h) {
+        int devices = 0;
+        const hipError_t e = hipGetDeviceCount(&devices);
+        if (e != hipSuccess || devices < 1) return fail(FPV_ENODEV, "no HIP device: detections run on the GPU only (fpv_detect_eval is the host function)");
+    }
+    rc = check_sensor(h, b, s, true, "object detection", "fpv_detect");
+    if (rc != FPV_OK) return rc;
+    A.state = b->state; A.ld = b->ld;
+    const DeviceGuard dev(h->device);
+    if (dev.rc != FPV_OK) return dev.rc;
+    void* arg = &A;
+    const dim3 grid((unsigned)((h->n + kStepBlock - 1) / kStepBlock), (unsigned)((A.count + FPV_DETECT_GROUP - 1) / FPV_DETECT_GROUP));
+    return launch_args("detection kernel launch", fpv_detect_kernel_fn(s->target_rows != nullptr), grid, dim3(kStepBlock), (hipStream_t)stream, &arg);
+}
+
+int fpv_detect_eval(const fpv_detect_t* s, int64_t n, const float* p, const float* q)
+{
+    if (fpv_detect_eval_host == nullptr) return fail(FPV_EINVAL, kDetectAbsent);
+    int rc = check_eval_args(s, n, p, q);
+    if (rc != FPV_OK) return rc;
+    FpvDetectArgs A;
+    rc = detect_args(s, n, &A);
+    if (rc != FPV_OK) return rc;
+    fpv_detect_eval_host(&A, p, q);
     return FPV_OK;
 }
 

@@ -72,6 +72,7 @@ class _Handle:
         self._keepalive = self._last_action = self._bcast_action = None
         self._last_action_ptr = 0
         self._depth_steps = 0           # steps since the last reset() of the env (FpvVecEnv.depth_every)
+        self._detect_steps = 0          # the same count for FpvVecEnv.detect_every
 
     def _pack(self, params: DroneParams, auto_reset: bool) -> _lib.FpvParams:
         return _lib.pack_params(params, auto_reset=auto_reset, **self._pack_kw)
@@ -242,7 +243,8 @@ class _Batch(_Handle):
                  with_action_out: bool = False, kahan_position: bool = False, per_drone_reset_pose: bool = False,
                  per_drone_physics: bool = False, gates: Any = None, laps: int = 0, gate_rewards: Optional[Dict[str, float]] = None,
                  miss_is_done: bool = False, gate_obs: bool = True, gate_start: Any = None, range_rays: Any = None,
-                 range_max: float = 20.0, depth_camera: Any = None, pursuit: Any = None):
+                 range_max: float = 20.0, depth_camera: Any = None, pursuit: Any = None, detector: Any = None,
+                 detect_slots: Optional[int] = None):
         if num_envs <= 0:
             raise ValueError("num_envs must be positive")
         device = torch.device(device)
@@ -358,6 +360,14 @@ class _Batch(_Handle):
         self.pursuit_pid_rows = self.pursuit_guidance = self._pursuit = self._pursuit_set = self._pursuit_chase = None
         if pursuit is not None:
             self._init_pursuit(pursuit)
+        # the object detections (fpv_detect_boxes; fpyv_amd.detect.BoxDetector): `box_rows` [slots, 4, ld], `box_depth_rows` [slots, ld]
+        # and `box_visible_rows` [slots, ld] bool the rows a detection writes - outputs: checkpoints do not carry them.  `detect_slots`
+        # is how many boxes the rows hold: by default the most an object list can bring (8), the gates of the course the batch is
+        # built with and the own-target slot
+        self.detector = detector
+        self.box_rows = self.box_depth_rows = self.box_visible_rows = self._detect = None
+        if detector is not None:
+            self._init_detector(detector, detect_slots)
 
     # -- plumbing ---------------------------------------------------------------------------------
     def _fill_buffers(self) -> None:
@@ -541,6 +551,13 @@ class _Batch(_Handle):
             if self._course is None or kw != self._course_kw or count != int(self._course.count):
                 self._course_kw = kw
                 self._bind_course(count)
+            if self._detect is not None:
+                # a checkpoint holds the descriptor rows, not the gates: unless they are the rows of the gates this batch knows, the
+                # next detection has nothing to box them from and says so (`_detect_world`) until set_gates() is called
+                from . import gates as _gates
+                known = self._gate_list or []
+                same = len(known) == count and np.array_equal(_gates.derive(known), self.gate_desc[:count].cpu().numpy())
+                self._gate_list, self._detect_key = (known if same else None), None
         self.set_step_counter(d["step_counter"])
 
     # -- gate courses ------------------------------------------------------------------------------
@@ -564,9 +581,12 @@ class _Batch(_Handle):
         if gates is None:
             _lib.check(self._L.fpv_set_gates(self._handle, None))
             self._course = None
+            self._gate_list, self._detect_key = [], None
             return
         from . import gates as _gates
         rows = _gates.derive(gates)
+        self._gate_list = list(gates)                       # what a detection boxes (fpyv_amd.detect): the gates as they stand now
+        self._detect_key = None
         self.gate_desc[:rows.shape[0]].copy_(torch.from_numpy(rows))
         if self._course is None or int(self._course.count) != rows.shape[0]:
             self._bind_course(rows.shape[0])
@@ -780,6 +800,74 @@ class _Batch(_Handle):
         self._render_world(object_list)
         self._depth_render_raw(self._render)
         return self.depth
+
+    # -- object detections -------------------------------------------------------------------------
+    def _init_detector(self, det, slots: Optional[int]) -> None:
+        own = bool(det.own_target)
+        if own and self._pursuit is None:
+            raise ValueError("BoxDetector(own_target=True) needs a batch built with pursuit=: the slot is the drone's own target")
+        cap = int(slots) if slots is not None else _lib.FPV_MAX_OBJECTS + len(getattr(self, "_gate_list", None) or ()) + int(own)
+        if not 1 <= cap <= _lib.FPV_MAX_BOXES:
+            raise ValueError(f"detect_slots must be 1..{_lib.FPV_MAX_BOXES}")
+        f32 = dict(dtype=torch.float32, device=self.device)
+        self.box_rows = torch.zeros((cap, 4, self.ld), **f32)
+        self.box_depth_rows = torch.zeros((cap, self.ld), **f32)
+        self.box_visible_rows = torch.zeros((cap, self.ld), dtype=torch.bool, device=self.device)   # the kernel writes exactly 0 or 1
+        s = det.derive()
+        s.boxes, s.box_depth, s.box_visible, s.ld = self.box_rows.data_ptr(), self.box_depth_rows.data_ptr(), self.box_visible_rows.data_ptr(), self.ld
+        if own:
+            s.target_rows, s.target_ld = self.target_position_rows.data_ptr(), self.ld
+            s.target_radius = self.target_rows.data_ptr() + 4 * _lib.TGT_RADIUS * self.ld
+        self._detect, self._detect_slots, self._detect_count = s, cap, 0
+        self._detect_list, self._detect_key, self._detect_table = [], None, None
+
+    def _detect_world(self, object_list, detect: Optional["_lib.FpvDetect"] = None) -> None:
+        """The box table of the next detection into `detect` (this batch's, or a partition's copy of it): the collidable entries of
+        `object_list` (None: the list of the last detection), then the gates of the course as `set_gates` last left them.  A world
+        that did not move is not boxed again."""
+        if self._detect is None:
+            raise ValueError("this batch was built without detector=")
+        if object_list is not None:
+            self._detect_list = list(object_list)
+        from .objects import to_rows
+        if getattr(self, "_course", None) is not None and getattr(self, "_gate_list", ()) is None:
+            raise ValueError("the gate course came from a checkpoint whose gates this batch was not given: call set_gates(gates) before "
+                             "detect() (a checkpoint holds the descriptor rows, which do not say what a detection boxes)")
+        gates = (getattr(self, "_gate_list", None) or []) if getattr(self, "_course", None) is not None else []
+        key = (to_rows(self._detect_list), tuple(float(getattr(o, "size", 0.0) or 0.0) for o in self._detect_list), len(gates))          # (set_gates clears the key)
+        if key != self._detect_key:
+            self._detect_table, self._detect_key = self.detector.table(self._detect_list, gates), key
+        m = int(self._detect_table.count) + int(self.detector.own_target)
+        if m > self._detect_slots:
+            raise ValueError(f"{m} boxes do not fit the {self._detect_slots} slots of this batch: build it with detect_slots={m}")
+        self._detect_count = m
+        (self._detect if detect is None else detect).table = C.addressof(self._detect_table)
+
+    def detect(self, object_list=None) -> torch.Tensor:
+        """One detection on torch's current stream: for every drone and every box - the Ground / Cylinder / Target entries of
+        `object_list` in order, the gates of the batch's course, with `BoxDetector(own_target=True)` the drone's own pursuit
+        target - the box (x_min, y_min, x_max, y_max) of its in-front corners in the drone's camera, the smallest in-front depth
+        and whether the reference's pruning rule keeps it.  Fills `boxes` [M, 4, num_envs], `box_depth` [M, num_envs] and
+        `box_visible` [M, num_envs]; returns `boxes`.  It reads the position and the attitude only: state, rewards, the step
+        counter and the rotation of the traversal are what they were (include/fpv_abi.h "Object detections")."""
+        self._detect_world(object_list)
+        self._sensor_raw(self._L.fpv_detect_boxes, self._detect, None)
+        return self.boxes
+
+    @property
+    def boxes(self) -> Optional[torch.Tensor]:
+        """[M, 4, num_envs] view of the box rows as the last detection wrote them (`.permute(2, 0, 1)`: a [num_envs, M, 4] block)"""
+        return None if self.box_rows is None else self.box_rows[:self._detect_count, :, :self.n]
+
+    @property
+    def box_depth(self) -> Optional[torch.Tensor]:
+        """[M, num_envs] view: the smallest in-front depth of every box, 0 with no corner in front"""
+        return None if self.box_depth_rows is None else self.box_depth_rows[:self._detect_count, :self.n]
+
+    @property
+    def box_visible(self) -> Optional[torch.Tensor]:
+        """[M, num_envs] bool view: the boxes the reference's pruned_objects_list keeps"""
+        return None if self.box_visible_rows is None else self.box_visible_rows[:self._detect_count, :self.n]
 
     # -- target chase ------------------------------------------------------------------------------
     def _chase_rows(self) -> torch.Tensor:
@@ -1165,6 +1253,12 @@ class _Partition(_Handle):
                 g = self._pursuit_chase = _lib.FpvChase.from_buffer_copy(pg)
                 g.pid_state, g.rotation, g.thrust = pg.pid_state + 4 * lo, pg.rotation + 36 * lo, pg.thrust + 4 * lo
                 t.guide = C.pointer(g)
+        self._detect = None
+        pd = getattr(self.parent, "_detect", None)     # the parent's detector on this partition's columns of the box rows
+        if pd is not None:
+            d = self._detect = _lib.FpvDetect.from_buffer_copy(pd)
+            d.boxes, d.box_depth, d.box_visible = pd.boxes + 4 * lo, pd.box_depth + 4 * lo, pd.box_visible + lo
+            d.target_rows, d.target_radius = off(pd.target_rows, 4), off(pd.target_radius, 4)
         self._render = None
         if self.parent._render is not None:            # the parent's camera on this partition's rows of the one image tensor
             r = self._render = _lib.FpvDepthRender.from_buffer_copy(self.parent._render)
@@ -1441,7 +1535,7 @@ class FpvVecEnv:
     def __init__(self, params: Optional[DroneParams] = None, num_envs: int = 1, device: Any = "cuda:0",
                  mode: str = "drone", auto_reset: bool = True, track_episodes: bool = True,
                  wind: Sequence[float] = (0.0, 0.0, 0.0), object_list=(), partitions: int = 1, depth_every: int = 1,
-                 guided: bool = False, assist: Any = None, assist_sticks: Sequence[float] = (0.0, 0.0, 0.0, 0.0), **batch_options: Any):
+                 detect_every: int = 1, guided: bool = False, assist: Any = None, assist_sticks: Sequence[float] = (0.0, 0.0, 0.0, 0.0), **batch_options: Any):
         """`batch_options` go to DroneBatch / RacerBatch (stick_noise=, noise_seed=, drone_id_offset=,
         fp16_state=, with_obs_aos=, kahan_position=, with_done_bits=, per_drone_physics=, ...); `object_list` is the
         collision world of every step (fpyv_amd.objects); `partitions` > 1 enables step_async / step_wait.  `range_rays=`
@@ -1451,7 +1545,11 @@ class FpvVecEnv:
         `depth_every`-th step are followed by a render of `object_list` and the gate course on the same stream (each partition
         into its rows of the one tensor), `depth` [num_envs, H, W] and info["depth"] hold the result; `depth_every=0` never renders
         by itself - call `render_depth()`.  With `depth_every=1` the image always belongs to `obs`: a lane that auto-reset shows
-        its reset pose.  `pursuit=` (a fpyv_amd.pursuit.PursuitTask) gives every drone a target of its own: reset() and every
+        its reset pose.  `detector=` (a fpyv_amd.detect.BoxDetector) adds the object detections in the same way: reset() and every
+        `detect_every`-th step are followed by a detection of `object_list`, the gate course and - with own_target=True - the
+        drone's own target on the same stream (after the pursuit call; each partition into its columns of the one tensor), `boxes`
+        [M, 4, num_envs], `box_depth`, `box_visible` and info["boxes" | "box_depth" | "box_visible"] hold the result;
+        `detect_every=0` never detects by itself - call `detect()`.  `pursuit=` (a fpyv_amd.pursuit.PursuitTask) gives every drone a target of its own: reset() and every
         step are followed by the pursuit call on the same stream (before the scan and the render), which adds the task's payment
         to `reward` and the episode return; `target_obs` [num_envs, 7], `target_position`, `target_event`, `captures` and
         info["target_obs" | "target_event" | "captures"] hold the result.  With `PursuitTask(guide=...)`, `guided=True` flies
@@ -1484,6 +1582,9 @@ class FpvVecEnv:
         if int(depth_every) < 0:
             raise ValueError("depth_every must be >= 0")
         self.depth_every = int(depth_every)
+        if int(detect_every) < 0:
+            raise ValueError("detect_every must be >= 0")
+        self.detect_every = int(detect_every)
         self.obs_dim = 13
         self.action_dim = 4
         self._obs_view = None
@@ -1620,7 +1721,8 @@ class FpvVecEnv:
         [num_envs, R] block a policy concatenates to `obs`"""
         return self.batch.ranges
 
-    def _sense(self, stepper: _Handle, stream: Optional[torch.cuda.Stream] = None, scan: bool = True, render: bool = True) -> None:
+    def _sense(self, stepper: _Handle, stream: Optional[torch.cuda.Stream] = None, scan: bool = True, render: bool = True,
+               detect: bool = False) -> None:
         """The sensors the env was built with after a step or a reset of `stepper` (the batch, or a partition on its own stream):
         the env's collision world and the batch's course as the batch packs them, the columns of `stepper`."""
         b = self.batch
@@ -1630,6 +1732,9 @@ class FpvVecEnv:
         if render and b.depth is not None:
             b._render_world(self.object_list, stepper._render)
             stepper._depth_render_raw(stepper._render, stream)
+        if detect and b.box_rows is not None:
+            b._detect_world(self.object_list, stepper._detect)
+            stepper._sensor_raw(stepper._L.fpv_detect_boxes, stepper._detect, stream)
 
     @property
     def depth(self) -> Optional[torch.Tensor]:
@@ -1637,10 +1742,11 @@ class FpvVecEnv:
         return self.batch.depth
 
     def _sense_after_reset(self) -> None:
-        """a reset() is followed by a scan and (unless depth_every = 0) a render of the whole population and restarts the count of steps"""
+        """a reset() is followed by a scan and (unless depth_every / detect_every = 0) a render and a detection of the whole
+        population and restarts the counts of steps"""
         for stepper in [self.batch] + self._parts:
-            stepper._depth_steps = 0
-        self._sense(self.batch, render=bool(self.depth_every))
+            stepper._depth_steps = stepper._detect_steps = 0
+        self._sense(self.batch, render=bool(self.depth_every), detect=bool(self.detect_every))
 
     def _sense_after_step(self, stepper: _Handle, stream: Optional[torch.cuda.Stream] = None) -> None:
         """every step of `stepper` is followed by the pursuit call (a batch built with pursuit=), then by a scan, every
@@ -1651,7 +1757,11 @@ class FpvVecEnv:
         if self.batch.depth is not None and self.depth_every:
             stepper._depth_steps += 1
             due = stepper._depth_steps % self.depth_every == 0
-        self._sense(stepper, stream, render=due)
+        seek = False
+        if self.batch.box_rows is not None and self.detect_every:
+            stepper._detect_steps += 1
+            seek = stepper._detect_steps % self.detect_every == 0
+        self._sense(stepper, stream, render=due, detect=seek)
 
     def render_depth(self) -> torch.Tensor:
         """Render every drone's image now, on the caller's stream, ordered after steps in flight like reset; returns `depth`."""
@@ -1659,6 +1769,26 @@ class FpvVecEnv:
             raise ValueError("this env was built without depth_camera=")
         self._whole_population(self._sense, self.batch, scan=False)
         return self.batch.depth
+
+    def detect(self) -> torch.Tensor:
+        """Detect for every drone now, on the caller's stream, ordered after steps in flight like reset; returns `boxes`."""
+        if self.batch.box_rows is None:
+            raise ValueError("this env was built without detector=")
+        self._whole_population(self._sense, self.batch, scan=False, render=False, detect=True)
+        return self.batch.boxes
+
+    @property
+    def boxes(self) -> Optional[torch.Tensor]:
+        """[M, 4, num_envs] the boxes after the last detection (None without detector=)"""
+        return self.batch.boxes
+
+    @property
+    def box_depth(self) -> Optional[torch.Tensor]:
+        return self.batch.box_depth
+
+    @property
+    def box_visible(self) -> Optional[torch.Tensor]:
+        return self.batch.box_visible
 
     def _whole_population(self, fn, *a, **kw) -> None:
         if not self._parts:
@@ -1717,6 +1847,10 @@ class FpvVecEnv:
             info["ranges"] = batch.range_rows[:, lo:hi]
         if getattr(batch, "depth", None) is not None:                  # the depth camera: [columns, H, W] after the last render
             info["depth"] = batch.depth[lo:hi]
+        if getattr(batch, "box_rows", None) is not None:               # the detections: [M, 4 | -, columns] after the last detection
+            m = batch._detect_count
+            info["boxes"], info["box_depth"] = batch.box_rows[:m, :, lo:hi], batch.box_depth_rows[:m, lo:hi]
+            info["box_visible"] = batch.box_visible_rows[:m, lo:hi]
         return info
 
     # -- split phase ------------------------------------------------------------------------------

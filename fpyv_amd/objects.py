@@ -12,7 +12,8 @@ Analytic counterparts of the reference's world classes, keeping only what `handl
 
 The rendering arguments (sizes of point clouds, icosphere subdivision, resolutions) are accepted so the
 reference's own call sites (src/core/simulator.py:53-58, src/utils/generators.py) construct these classes
-unchanged, and are ignored: point clouds, rendering and bounding boxes are out of scope.  Gates and the
+unchanged, and are ignored: point clouds and rendering are out of scope (the image-plane bounding boxes of these objects are
+`fpyv_amd.detect`; a Ground's `size` is the one rendering argument they read).  Gates and the
 Trail never collide in the reference (components.py:202): `to_rows` skips them, so an `object_list` built by the
 reference's code can be passed as is.  A Gate keeps the reference's plane geometry (normal, calculate_distance) and
 describes itself to the gate-course kernels (`as_gate_row`, fpyv_amd.gates).

@@ -315,7 +315,7 @@ typedef struct fpv_env* fpv_handle_t;
 int fpv_abi_version(void);
 /* sizeof of the ABI structs as this library was compiled (0 fpv_params_t, 1 fpv_buffers_t, 2 fpv_objects_t,
  * 3 fpv_pid_params_t, 4 fpv_cache_model_t, 5 fpv_gate_course_t, 6 fpv_range_scan_t, 7 fpv_depth_render_t, 8 fpv_chase_t,
- * 10 fpv_pursuit_t, 12 fpv_pns_t):
+ * 10 fpv_pursuit_t, 12 fpv_pns_t, 14 fpv_detect_t, 16 fpv_boxes_t):
  * lets a foreign-language binding verify its struct declarations at load time */
 int fpv_sizeof(int which);
 /* rows of the state matrix for a mode (FPV_DRONE_ROWS / FPV_RACER_ROWS), or FPV_EINVAL */
@@ -903,6 +903,68 @@ int fpv_pns_guide(fpv_handle_t h, const fpv_buffers_t* b, const fpv_pns_t* s, vo
 /* The kernel's own lane function on the host (no handle, no device): drone i of n at p[i][3] with velocity v[i][3] and attitude
  * q[i][4] (wxyz); every pointer of *s is HOST memory. */
 int fpv_pns_eval(const fpv_pns_t* s, int64_t n, const float* p /*[n][3]*/, const float* v /*[n][3]*/, const float* q /*[n][4] wxyz*/);
+
+/* ---- Object detections: the 2-D box of every object and gate in every drone's camera (functions and two structs only -
+ * FPV_ABI_VERSION, fpv_params_t, fpv_buffers_t and fpv_objects_t are those of ABI 9) ---------------------------------------------------
+ * The reference's Camera.project(attr='bbox3d'), bbox3d_to_bbox2d and pruned_objects_list (components.py:558-600) for N drones: for
+ * a drone pose and an axis-aligned world box (min[3], max[3]) the eight corners in the reference's order (helper_functions.py:126-132)
+ * are taken into the camera frame, c = Rcam^T (X - pcam) with pcam = p + R(q) rel_pos and Rcam = R(q) rel_rot (Camera.update); a
+ * corner is in front when c.z > 0, its pixel is ((f c.x) / c.z + W/2, (f c.y) / c.z + H/2).  The box is the componentwise min and max
+ * over the in-front corners, depth the smallest in-front c.z, visible the reference's pruning rule: a corner in front and
+ * x_max > 0, y_max > 0, x_min < W, y_min < H.  With no corner in front (the reference's bbox2d raises) the box is (0, 0, 0, 0), depth 0,
+ * visible 0.  FPV_DETECT_INT truncates every pixel coordinate toward zero (the reference's astype(int)) and keeps it a float;
+ * FPV_DETECT_FLOAT keeps the sub-pixel value.  clip != 0 clamps a VISIBLE box to [0, W] x [0, H] (the reference does not clip).
+ * csrc/fpv_detect.h is the ONE definition the kernel (csrc/fpv_detect.hip: a lane is a drone, blockIdx.y a group of 8 slots) and
+ * fpv_detect_eval run: the same bits.  Like the range scan it reads p and q only: it serves every fp32 handle and leaves the state,
+ * the step counter and the rotation alone; it moves 28 + 21 M bytes per drone for M boxes.
+ * Slots: the boxes of `table` in order (fpv_boxes_derive: the collidable objects of the list, then the gates of the course), then -
+ * target_rows given - the lane's OWN box, centre +- radius around target_rows[0..2][i] (the layout fpv_pursuit_t.position writes),
+ * radius = target_radius[i] or, without that row, target_radius_all. */
+#define FPV_MAX_BOXES (FPV_MAX_OBJECTS + FPV_MAX_GATES)
+enum { FPV_DETECT_INT = 0, FPV_DETECT_FLOAT = 1 };
+typedef struct fpv_boxes { int32_t count; float box[FPV_MAX_BOXES][6]; } fpv_boxes_t;   /* box: min x, y, z, max x, y, z; fpv_sizeof(16) */
+typedef struct fpv_detect {
+    uint32_t struct_size;            /* sizeof(fpv_detect_t) = fpv_sizeof(14) (13 stays "no such struct") */
+    int32_t  width, height;          /* written by fpv_detect_derive, like the three camera fields below */
+    int32_t  pixel_mode;             /* FPV_DETECT_INT / FPV_DETECT_FLOAT */
+    int32_t  clip;                   /* != 0: clamp visible boxes to the image */
+    int32_t  _reserved;
+    double   focal_length;
+    double   relative_rotation[9];
+    double   relative_position[3];
+    const fpv_boxes_t* table;        /* HOST memory, read during the call; NULL or count 0: only the own-target slot */
+    const float* target_rows;        /* [3][target_ld] or NULL = no own-target slot; DEVICE for fpv_detect_boxes, HOST for fpv_detect_eval */
+    int64_t  target_ld;              /* >= n */
+    const float* target_radius;      /* [n] a radius per drone, or NULL = target_radius_all (DEVICE / HOST like target_rows) */
+    float    target_radius_all;      /* finite, >= 0 */
+    float    _reserved2;
+    float*   boxes;                  /* [M][4][ld] x_min, y_min, x_max, y_max; write-only; DEVICE / HOST like target_rows; 4-byte aligned */
+    float*   box_depth;              /* [M][ld] */
+    uint8_t* box_visible;            /* [M][ld] exactly 0 or 1 */
+    int64_t  ld;                     /* >= n, multiple of 4; columns n..ld-1 and slots >= M are not written */
+} fpv_detect_t;
+/* The box table of an object list and a course (host arithmetic only, double, narrowed once): first objects->obj[k] in order -
+ * Ground: [-size/2, size/2]^2 x {0} with size = ground_size[k] (the reference's grid cloud); Cylinder: [x +- r, y +- r, z .. z + h]
+ * (the reference's cloud when angle_resolution = 1 mod 4); Sphere: centre +- radius (what the box of the reference's icosphere tends
+ * to) -, then gates[g] in order: the box of the reference's own corner points (components.py:790-805) at gate_resolution (17 is the
+ * reference's) - rectangle, circle and half_circle with its radius `size` and its -size/2 shift.  objects and gates may be NULL with
+ * no entries.  FPV_EPARAM, naming the slot ("box <index>: ..."): a Ground without ground_size or with a size that is not positive, a radius or height that makes
+ * min > max, a box that is not finite, an unknown type or shape, gate_resolution outside 1..4096, more than FPV_MAX_BOXES boxes. */
+int fpv_boxes_derive(const fpv_objects_t* objects, const double* ground_size /*[objects->count] or NULL*/, const fpv_gate_t* gates,
+                     int gate_count, int gate_resolution, fpv_boxes_t* out);
+/* Fills width, height, focal_length, relative_rotation and relative_position of *out with what fpv_chase_derive computes for the
+ * camera (host arithmetic only; the reference's 640 x 480 is accepted; every other field is left alone). */
+int fpv_detect_derive(const fpv_camera_t* camera, fpv_detect_t* out);
+/* One detection of the handle's n drones at b->state / b->ld on `stream`, under the handle's device: allocates nothing, never
+ * synchronises, does not advance the step index and does not touch the rotation.  The struct is checked before the handle is
+ * looked at.  FPV_EINVAL / FPV_EALIGN / FPV_EPARAM, by name: null or misaligned outputs, ld < n or not a multiple of 4, a count
+ * (table + own slot) outside 1..FPV_MAX_BOXES, a box that is not finite or has min > max, camera numbers that are not
+ * fpv_detect_derive's, an unknown pixel mode, fp16 state; FPV_ENODEV for a null handle where there is no device; and in a library
+ * built without csrc/fpv_detect.hip. */
+int fpv_detect_boxes(fpv_handle_t h, const fpv_buffers_t* b, const fpv_detect_t* s, void* stream);
+/* The kernel's own lane function on the host (no handle, no device): drone i of n at p[i][3] with attitude q[i][4] (wxyz); every
+ * pointer of *s is HOST memory. */
+int fpv_detect_eval(const fpv_detect_t* s, int64_t n, const float* p /*[n][3]*/, const float* q /*[n][4] wxyz*/);
 
 const char* fpv_last_error(void);
 const char* fpv_error_name(int code);
