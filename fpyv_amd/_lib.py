@@ -64,7 +64,8 @@ EXPORTS = ("fpv_abi_version", "fpv_sizeof", "fpv_state_rows", "fpv_algorithmic_b
            "fpv_chase_derive", "fpv_chase_guide", "fpv_chase_eval",
            "fpv_pursuit_derive", "fpv_pursuit_sample", "fpv_pursuit_step", "fpv_pursuit_reset", "fpv_pursuit_eval",
            "fpv_pns_derive", "fpv_pns_guide", "fpv_pns_eval",
-           "fpv_boxes_derive", "fpv_detect_derive", "fpv_detect_boxes", "fpv_detect_eval")
+           "fpv_boxes_derive", "fpv_detect_derive", "fpv_detect_boxes", "fpv_detect_eval",
+           "fpv_splat_derive", "fpv_cloud_derive", "fpv_splat_render", "fpv_splat_eval")
 
 
 class FpvParams(C.Structure):
@@ -321,6 +322,21 @@ class FpvDetect(C.Structure):
                 ("box_depth", C.c_void_p), ("box_visible", C.c_void_p), ("ld", C.c_int64)]
 
 
+FPV_SPLAT_MAX_POINTS = 1 << 20                      # fpv_splat_t: the points of a cloud (fpv_abi.h "Point-cloud camera")
+SPLAT_ENCODINGS = {"metres": 0, "u8": 1, "mask": 2}
+CLOUD_GROUND, CLOUD_CYLINDER, CLOUD_GATE = 0, 1, 2
+
+
+class FpvSplat(C.Structure):
+    """fpv_splat_t: the camera numbers fpv_splat_derive computes, max_depth and the encoding, the object tables by value (first,
+    offset, box), the SoA points, the image and the optional centroid and lit (device for fpv_splat_render, host for fpv_splat_eval)."""
+    _fields_ = [("struct_size", C.c_uint32), ("width", C.c_int32), ("height", C.c_int32), ("encoding", C.c_int32), ("max_depth", C.c_float),
+                ("object_count", C.c_int32), ("focal_length", C.c_double), ("relative_rotation", C.c_double * 9),
+                ("relative_position", C.c_double * 3), ("first", C.c_int32 * (FPV_MAX_BOXES + 1)), ("_reserved", C.c_int32),
+                ("offset", (C.c_float * 3) * FPV_MAX_BOXES), ("box", (C.c_float * 6) * FPV_MAX_BOXES), ("points", C.c_void_p),
+                ("point_ld", C.c_int64), ("image", C.c_void_p), ("image_ld", C.c_int64), ("centroid", C.c_void_p), ("lit", C.c_void_p)]
+
+
 class FpvPursuit(C.Structure):
     """fpv_pursuit_t: the path table, the rewards, the spawn box and the flags of a pursuit call, the target rows and the optional
     outputs (device for fpv_pursuit_step / _reset, host for fpv_pursuit_eval), and the optional guidance law (a fpv_chase_t)."""
@@ -440,12 +456,16 @@ def lib() -> C.CDLL:
     L.fpv_detect_derive.argtypes = [C.POINTER(FpvCamera), C.POINTER(FpvDetect)]
     L.fpv_detect_boxes.argtypes = [vp, pb, C.POINTER(FpvDetect), vp]
     L.fpv_detect_eval.argtypes = [C.POINTER(FpvDetect), i64, vp, vp]
+    L.fpv_splat_derive.argtypes = [C.POINTER(FpvCamera), C.POINTER(FpvSplat)]
+    L.fpv_cloud_derive.argtypes = [C.c_int, vp, vp, vp, i64]
+    L.fpv_splat_render.argtypes = [vp, pb, C.POINTER(FpvSplat), vp]
+    L.fpv_splat_eval.argtypes = [C.POINTER(FpvSplat), i64, vp, vp]
     if L.fpv_abi_version() != FPV_ABI_VERSION:
         raise ImportError(f"libfpv_hip.so ABI {L.fpv_abi_version()} != binding {FPV_ABI_VERSION} - rebuild the library "
                           "(`python -c 'import __graft_entry__ as g; g.build()'`)")
     for which, struct in ((0, FpvParams), (1, FpvBuffers), (2, FpvObjects), (3, FpvPidParams), (4, FpvCacheModel), (5, FpvGateCourse),
                           (6, FpvRangeScan), (7, FpvDepthRender), (8, FpvChase), (10, FpvPursuit), (12, FpvPns), (14, FpvDetect),
-                          (16, FpvBoxes)):
+                          (16, FpvBoxes), (18, FpvSplat)):
         if L.fpv_sizeof(which) != C.sizeof(struct):
             raise ImportError(f"{struct.__name__}: ctypes declares {C.sizeof(struct)} bytes, libfpv_hip.so has "
                               f"{L.fpv_sizeof(which)} - _lib.py and include/fpv_abi.h are out of step")

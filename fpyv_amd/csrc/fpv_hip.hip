@@ -40,6 +40,7 @@
 #include "fpv_chase.h"
 #include "fpv_pns.h"
 #include "fpv_detect.h"
+#include "fpv_splat.h"
 #include "fpv_pursuit.h"
 
 namespace {
@@ -875,6 +876,9 @@ extern "C" __attribute__((weak, visibility("hidden"))) void fpv_pns_eval_host(co
 // The kernels of csrc/fpv_detect.hip (with and without the own-target slot) and its host loop, weak in the same way: one FpvDetectArgs.
 extern "C" __attribute__((weak, visibility("hidden"))) void* fpv_detect_kernel_fn(int own);
 extern "C" __attribute__((weak, visibility("hidden"))) void fpv_detect_eval_host(const FpvDetectArgs* A, const float* p, const float* q);
+// The kernel of csrc/fpv_splat.hip and its host loop, weak in the same way: one FpvSplatArgs.
+extern "C" __attribute__((weak, visibility("hidden"))) void* fpv_splat_kernel_fn(void);
+extern "C" __attribute__((weak, visibility("hidden"))) void fpv_splat_eval_host(const FpvSplatArgs* A, const float* p, const float* q);
 // The kernels of csrc/fpv_pursuit.hip ([guidance law][reset call]) and its host loop, weak in the same way (fpv_pursuit_step, _reset
 // and _eval say so when they are absent): one FpvPursuitArgs.
 extern "C" __attribute__((weak, visibility("hidden"))) void* fpv_pursuit_kernel_fn(int guide, int reset);
@@ -1449,7 +1453,8 @@ int fpv_sizeof(int which)
         case 12: return (int)sizeof(fpv_pns_t);            // 11 stays refused like 9
         case 14: return (int)sizeof(fpv_detect_t);         // 13 and 15 stay refused like 9
         case 16: return (int)sizeof(fpv_boxes_t);
-        default: return fail(FPV_EINVAL, "fpv_sizeof: 0 = fpv_params_t, 1 = fpv_buffers_t, 2 = fpv_objects_t, 3 = fpv_pid_params_t, 4 = fpv_cache_model_t, 5 = fpv_gate_course_t, 6 = fpv_range_scan_t, 7 = fpv_depth_render_t, 8 = fpv_chase_t, 10 = fpv_pursuit_t, 12 = fpv_pns_t, 14 = fpv_detect_t, 16 = fpv_boxes_t");
+        case 18: return (int)sizeof(fpv_splat_t);          // 17 stays refused like 9
+        default: return fail(FPV_EINVAL, "fpv_sizeof: 0 = fpv_params_t, 1 = fpv_buffers_t, 2 = fpv_objects_t, 3 = fpv_pid_params_t, 4 = fpv_cache_model_t, 5 = fpv_gate_course_t, 6 = fpv_range_scan_t, 7 = fpv_depth_render_t, 8 = fpv_chase_t, 10 = fpv_pursuit_t, 12 = fpv_pns_t, 14 = fpv_detect_t, 16 = fpv_boxes_t, 18 = fpv_splat_t");
     }
 }
 
@@ -2144,6 +2149,137 @@ int fpv_detect_eval(const fpv_detect_t* s, int64_t n, const float* p, const floa
     rc = detect_args(s, n, &A);
     if (rc != FPV_OK) return rc;
     fpv_detect_eval_host(&A, p, q);
+    return FPV_OK;
+}
+
+int fpv_splat_derive(const fpv_camera_t* camera, fpv_splat_t* out)
+{
+    if (!camera || !out) return fail(FPV_EINVAL, "null argument");
+    if (camera->width < 4 || camera->width > FPV_DEPTH_MAX_SIDE || camera->height < 4 || camera->height > FPV_DEPTH_MAX_SIDE)
+        return fail(FPV_EPARAM, "width and height must be 4..128 pixels: the z-buffer of a drone is an LDS image");
+    if (camera->width % 4) return fail(FPV_EPARAM, "width must be a multiple of 4");
+    fpv_chase_t c;
+    const int rc = fpv_chase_derive(camera, &c);
+    if (rc != FPV_OK) return rc;
+    out->width = c.width; out->height = c.height; out->focal_length = c.focal_length;
+    memcpy(out->relative_rotation, c.relative_rotation, sizeof c.relative_rotation);
+    memcpy(out->relative_position, c.relative_position, sizeof c.relative_position);
+    return FPV_OK;
+}
+
+int fpv_cloud_derive(int kind, const double* numbers, const int32_t* resolutions, float* out_points, int64_t ld)
+{
+    if (!numbers || !resolutions) return fail(FPV_EINVAL, "null argument");
+    if (kind < FPV_CLOUD_GROUND || kind > FPV_CLOUD_GATE) return fail(FPV_EINVAL, "unknown cloud kind");
+    const int nn = kind == FPV_CLOUD_GROUND ? 1 : kind == FPV_CLOUD_CYLINDER ? 5 : 13;
+    for (int k = 0; k < nn; ++k)
+        if (!isfinite(numbers[k])) return fail(FPV_EPARAM, "the numbers of a cloud must be finite");
+    if (kind == FPV_CLOUD_GATE && (resolutions[0] < FPV_GATE_RECTANGLE || resolutions[0] > FPV_GATE_HALF_CIRCLE)) return fail(FPV_EPARAM, "unknown gate shape");
+    const int nr = kind == FPV_CLOUD_GROUND ? 1 : 2;
+    for (int k = kind == FPV_CLOUD_GATE ? 1 : 0; k < nr; ++k)
+        if (resolutions[k] < 1 || resolutions[k] > FPV_SPLAT_MAX_POINTS) return fail(FPV_EPARAM, "a resolution must be 1..2^20");
+    const int64_t count = fpv_cloud_points(kind, numbers, resolutions, nullptr, 0);
+    if (count > FPV_SPLAT_MAX_POINTS) return fail(FPV_EPARAM, "a cloud has at most 2^20 points");
+    if (!out_points) return (int)count;
+    if (ld < count) return fail(FPV_EALIGN, "ld is smaller than the number of points");
+    if (ld % 4) return fail(FPV_EALIGN, "ld must be a multiple of 4");
+    if ((uintptr_t)out_points & 3) return fail(FPV_EALIGN, "out_points must be 4-byte aligned");
+    return (int)fpv_cloud_points(kind, numbers, resolutions, out_points, ld);
+}
+
+namespace {
+
+const char kSplatAbsent[] = "the point-cloud camera is not in this build (the library was linked without csrc/fpv_splat.hip)";
+
+// the uniform constants of a call, its object tables and its buffers, checked: FPV_OK or the error
+int splat_args(const fpv_splat_t* s, int64_t n, FpvSplatArgs* A)
+{
+    if (s->struct_size != sizeof(fpv_splat_t)) return fail(FPV_EINVAL, "fpv_splat_t.struct_size does not match this library");
+    if (s->width < 4 || s->width > FPV_DEPTH_MAX_SIDE || s->height < 4 || s->height > FPV_DEPTH_MAX_SIDE)
+        return fail(FPV_EPARAM, "width and height must be 4..128 pixels (the camera numbers come from fpv_splat_derive)");
+    if (s->width % 4) return fail(FPV_EPARAM, "width must be a multiple of 4");
+    if (!isfinite(s->focal_length) || !(s->focal_length > 0.0)) return fail(FPV_EPARAM, "focal_length must be finite and positive (fpv_splat_derive)");
+    for (int k = 0; k < 9; ++k)
+        if (!isfinite(s->relative_rotation[k])) return fail(FPV_EPARAM, "relative_rotation is not finite");
+    for (int k = 0; k < 3; ++k)
+        if (!isfinite(s->relative_position[k])) return fail(FPV_EPARAM, "relative_position is not finite");
+    if (s->encoding != FPV_SPLAT_METRES && s->encoding != FPV_SPLAT_U8 && s->encoding != FPV_SPLAT_MASK) return fail(FPV_EINVAL, "unknown encoding");
+    if (!isfinite(s->max_depth) || !(s->max_depth > 0.0f)) return fail(FPV_EPARAM, "max_depth must be finite and positive");
+    const int M = s->object_count;
+    if (M < 0 || M > FPV_MAX_BOXES) return fail(FPV_EINVAL, "object_count: a cloud has 0.." + std::to_string(FPV_MAX_BOXES) + " objects, not " + std::to_string(M));
+    if (s->first[0] != 0) return fail(FPV_EPARAM, "first[0] must be 0");
+    for (int m = 0; m < M; ++m) {
+        if (s->first[m + 1] < s->first[m]) return fail(FPV_EPARAM, "first is not non-decreasing at object " + std::to_string(m));
+        if (s->first[m + 1] > FPV_SPLAT_MAX_POINTS) return fail(FPV_EPARAM, "first is past 2^20 points at object " + std::to_string(m));
+        for (int a = 0; a < 6; ++a)
+            if (!isfinite(s->box[m][a])) return fail(FPV_EPARAM, "box " + std::to_string(m) + " is not finite");
+        for (int a = 0; a < 3; ++a) {
+            if (s->box[m][a] > s->box[m][3 + a]) return fail(FPV_EPARAM, "box " + std::to_string(m) + " has min > max");
+            if (!isfinite(s->offset[m][a])) return fail(FPV_EPARAM, "offset " + std::to_string(m) + " is not finite");
+        }
+    }
+    const int32_t total = s->first[M];
+    if (total > 0 && !s->points) return fail(FPV_EINVAL, "fpv_splat_t.points is null");
+    if ((uintptr_t)s->points & 3) return fail(FPV_EALIGN, "points must be 4-byte aligned");
+    if (s->point_ld < total) return fail(FPV_EALIGN, "point_ld is smaller than the number of points");
+    if (s->point_ld % 4) return fail(FPV_EALIGN, "point_ld must be a multiple of 4");
+    if (!s->image) return fail(FPV_EINVAL, "fpv_splat_t.image is null");
+    if ((uintptr_t)s->image & 3) return fail(FPV_EALIGN, "image must be 4-byte aligned");
+    if (s->image_ld < (int64_t)s->width * s->height) return fail(FPV_EALIGN, "image_ld is smaller than width * height");
+    if (s->image_ld % 4) return fail(FPV_EALIGN, "image_ld must be a multiple of 4 elements");
+    if ((s->centroid == nullptr) != (s->lit == nullptr)) return fail(FPV_EINVAL, "centroid and lit are given together or not at all");
+    if (((uintptr_t)s->centroid & 3) || ((uintptr_t)s->lit & 3)) return fail(FPV_EALIGN, "centroid and lit must be 4-byte aligned");
+    if (n > 0x7fffffff) return fail(FPV_EINVAL, "more than 2^31 - 1 drones (a workgroup each): render the population in parts");
+    memset(A, 0, sizeof(*A));
+    FpvDetectK& K = A->K;
+    for (int k = 0; k < 9; ++k) K.rr[k] = (float)s->relative_rotation[k];
+    for (int k = 0; k < 3; ++k) K.rel[k] = (float)s->relative_position[k];
+    K.f = (float)s->focal_length; K.cx = (float)(s->width / 2.0); K.cy = (float)(s->height / 2.0);
+    K.w = (float)s->width; K.h = (float)s->height;
+    K.trunc = 1; K.clip = 0;
+    A->max_depth = s->max_depth; A->encoding = s->encoding; A->width = s->width; A->height = s->height; A->count = M;
+    memcpy(A->first, s->first, sizeof(int32_t) * (size_t)(M + 1));
+    if (M) { memcpy(A->offset, s->offset, sizeof(float) * 3 * (size_t)M); memcpy(A->box, s->box, sizeof(float) * 6 * (size_t)M); }
+    A->points = s->points; A->point_ld = s->point_ld; A->image = s->image; A->image_ld = s->image_ld;
+    A->centroid = s->centroid; A->lit = s->lit; A->n = n;
+    return FPV_OK;
+}
+
+}  // namespace
+
+int fpv_splat_render(fpv_handle_t h, const fpv_buffers_t* b, const fpv_splat_t* s, void* stream)
+{
+    if (fpv_splat_kernel_fn == nullptr) return fail(FPV_EINVAL, kSplatAbsent);
+    if (!s) return fail(FPV_EINVAL, "null argument");
+    FpvSplatArgs A;
+    int rc = splat_args(s, h ? h->n : 1, &A);              // the struct first: what it refuses needs no device
+    if (rc != FPV_OK) return rc;
+    if (!h) {
+        int devices = 0;
+        const hipError_t e = hipGetDeviceCount(&devices);
+        if (e != hipSuccess || devices < 1) return fail(FPV_ENODEV, "no HIP device: the point-cloud camera renders on the GPU only (fpv_splat_eval is the host function)");
+    }
+    rc = check_sensor(h, b, s, true, "point-cloud camera", "fpv_splat");
+    if (rc != FPV_OK) return rc;
+    A.state = b->state; A.ld = b->ld;
+    const DeviceGuard dev(h->device);
+    if (dev.rc != FPV_OK) return dev.rc;
+    void* arg = &A;
+    const size_t lds = sizeof(uint32_t) * (size_t)s->width * (size_t)s->height;      // the z-buffer: at most 64 KiB
+    (void)hipLaunchKernel(fpv_splat_kernel_fn(), dim3((unsigned)h->n), dim3(FPV_SPLAT_BLOCK), &arg, lds, (hipStream_t)stream);
+    const hipError_t e = hipGetLastError();
+    return e == hipSuccess ? FPV_OK : hip_fail(e, "point-cloud render launch");
+}
+
+int fpv_splat_eval(const fpv_splat_t* s, int64_t n, const float* p, const float* q)
+{
+    if (fpv_splat_eval_host == nullptr) return fail(FPV_EINVAL, kSplatAbsent);
+    int rc = check_eval_args(s, n, p, q);
+    if (rc != FPV_OK) return rc;
+    FpvSplatArgs A;
+    rc = splat_args(s, n, &A);
+    if (rc != FPV_OK) return rc;
+    fpv_splat_eval_host(&A, p, q);
     return FPV_OK;
 }
 

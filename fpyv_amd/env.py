@@ -73,6 +73,7 @@ class _Handle:
         self._last_action_ptr = 0
         self._depth_steps = 0           # steps since the last reset() of the env (FpvVecEnv.depth_every)
         self._detect_steps = 0          # the same count for FpvVecEnv.detect_every
+        self._cloud_steps = 0           # ... and for FpvVecEnv.cloud_every
 
     def _pack(self, params: DroneParams, auto_reset: bool) -> _lib.FpvParams:
         return _lib.pack_params(params, auto_reset=auto_reset, **self._pack_kw)
@@ -244,7 +245,7 @@ class _Batch(_Handle):
                  per_drone_physics: bool = False, gates: Any = None, laps: int = 0, gate_rewards: Optional[Dict[str, float]] = None,
                  miss_is_done: bool = False, gate_obs: bool = True, gate_start: Any = None, range_rays: Any = None,
                  range_max: float = 20.0, depth_camera: Any = None, pursuit: Any = None, detector: Any = None,
-                 detect_slots: Optional[int] = None):
+                 detect_slots: Optional[int] = None, cloud_camera: Any = None):
         if num_envs <= 0:
             raise ValueError("num_envs must be positive")
         device = torch.device(device)
@@ -368,6 +369,12 @@ class _Batch(_Handle):
         self.box_rows = self.box_depth_rows = self.box_visible_rows = self._detect = None
         if detector is not None:
             self._init_detector(detector, detect_slots)
+        # the point-cloud camera (fpv_splat_render; fpyv_amd.splat.PointCloudCamera): `points_image` [num_envs, H, W] uint8 or float32
+        # and - PointCloudCamera(centroid=True) - `points_centroid` [num_envs, 2], `points_lit` [num_envs]: outputs, not in checkpoints
+        self.cloud_camera = cloud_camera
+        self.points_image = self.points_centroid = self.points_lit = self._splat = None
+        if cloud_camera is not None:
+            self._init_cloud_camera(cloud_camera)
 
     # -- plumbing ---------------------------------------------------------------------------------
     def _fill_buffers(self) -> None:
@@ -581,12 +588,12 @@ class _Batch(_Handle):
         if gates is None:
             _lib.check(self._L.fpv_set_gates(self._handle, None))
             self._course = None
-            self._gate_list, self._detect_key = [], None
+            self._gate_list, self._detect_key, self._cloud_key = [], None, None
             return
         from . import gates as _gates
         rows = _gates.derive(gates)
         self._gate_list = list(gates)                       # what a detection boxes (fpyv_amd.detect): the gates as they stand now
-        self._detect_key = None
+        self._detect_key = self._cloud_key = None           # ... and what the point-cloud camera splats (fpyv_amd.splat)
         self.gate_desc[:rows.shape[0]].copy_(torch.from_numpy(rows))
         if self._course is None or int(self._course.count) != rows.shape[0]:
             self._bind_course(rows.shape[0])
@@ -868,6 +875,55 @@ class _Batch(_Handle):
     def box_visible(self) -> Optional[torch.Tensor]:
         """[M, num_envs] bool view: the boxes the reference's pruned_objects_list keeps"""
         return None if self.box_visible_rows is None else self.box_visible_rows[:self._detect_count, :self.n]
+
+    # -- point-cloud camera ------------------------------------------------------------------------
+    def _init_cloud_camera(self, cam) -> None:
+        s = cam.derive()
+        w, h = cam.resolution
+        self.points_image = torch.zeros((self.n, h, w), dtype=torch.float32 if cam.encoding == "metres" else torch.uint8, device=self.device)
+        s.image, s.image_ld = self.points_image.data_ptr(), w * h
+        if cam.centroid:
+            self.points_centroid = torch.zeros((self.n, 2), dtype=torch.float32, device=self.device)
+            self.points_lit = torch.zeros((self.n,), dtype=torch.int32, device=self.device)
+            s.centroid, s.lit = self.points_centroid.data_ptr(), self.points_lit.data_ptr()
+        self._splat = s
+        self._cloud = self._cloud_key = self._cloud_held = self._cloud_dev = self._cloud_dev_of = None
+
+    def _cloud_world(self, world, splat: Optional["_lib.FpvSplat"] = None) -> None:
+        """The cloud of the next render into `splat` (this batch's, or a partition's copy of it).  `world` a PointCloud: taken as it
+        is.  An object list: its clouds in list order (PointCloud.from_world), then the points of the course's gates as `set_gates`
+        last left them; a list of the same objects as last time is not flattened or uploaded again - only the Targets' offsets are
+        read anew (an object whose points changed in place needs a new list or a PointCloud).  None: the world of the last render,
+        the empty one if there was none."""
+        if self._splat is None:
+            raise ValueError("this batch was built without cloud_camera=")
+        from .clouds import PointCloud
+        if isinstance(world, PointCloud):
+            self._cloud, self._cloud_key = world, None
+        elif world is not None or self._cloud is None:
+            objs = list(world or ())
+            gates = (getattr(self, "_gate_list", None) or []) if getattr(self, "_course", None) is not None else []
+            key = tuple(id(o) for o in objs) + (len(gates),)                    # (set_gates clears the key)
+            if key != self._cloud_key:
+                self._cloud, self._cloud_key, self._cloud_held = PointCloud.from_world(objs, gates), key, objs
+        cloud = self._cloud
+        cloud.refresh()
+        if self._cloud_dev_of is not cloud:
+            # a new tensor every time: a render in flight on another stream keeps reading the one it was given
+            self._cloud_dev, self._cloud_dev_of = torch.from_numpy(cloud.points).to(self.device), cloud
+        s = self._splat if splat is None else splat
+        cloud.fill(s)
+        s.points = self._cloud_dev.data_ptr()
+
+    def render_points(self, cloud_or_object_list=None) -> torch.Tensor:
+        """One image per drone on torch's current stream: the reference's splatted image (Camera.render_depth_image / render_image)
+        of the point clouds of `cloud_or_object_list` - a fpyv_amd.clouds.PointCloud, or an object list whose entries have `points`
+        (with the batch's gate course after them); None renders the last world again, a moved Target where it is now.  Returns
+        `points_image` [num_envs, H, W]; PointCloudCamera(centroid=True) also fills `points_centroid` and `points_lit`.  The render
+        reads the position and the attitude only (include/fpv_abi.h "Point-cloud camera")."""
+        self._cloud_world(cloud_or_object_list)
+        self._sensor_raw(self._L.fpv_splat_render, self._splat, None)
+        return self.points_image
 
     # -- target chase ------------------------------------------------------------------------------
     def _chase_rows(self) -> torch.Tensor:
@@ -1259,6 +1315,12 @@ class _Partition(_Handle):
             d = self._detect = _lib.FpvDetect.from_buffer_copy(pd)
             d.boxes, d.box_depth, d.box_visible = pd.boxes + 4 * lo, pd.box_depth + 4 * lo, pd.box_visible + lo
             d.target_rows, d.target_radius = off(pd.target_rows, 4), off(pd.target_radius, 4)
+        self._splat = None
+        ps = getattr(self.parent, "_splat", None)      # the parent's point-cloud camera on this partition's rows of its outputs
+        if ps is not None:
+            c = self._splat = _lib.FpvSplat.from_buffer_copy(ps)
+            c.image = ps.image + lo * ps.image_ld * self.parent.points_image.element_size()
+            c.centroid, c.lit = off(ps.centroid, 8), off(ps.lit, 4)
         self._render = None
         if self.parent._render is not None:            # the parent's camera on this partition's rows of the one image tensor
             r = self._render = _lib.FpvDepthRender.from_buffer_copy(self.parent._render)
@@ -1535,7 +1597,7 @@ class FpvVecEnv:
     def __init__(self, params: Optional[DroneParams] = None, num_envs: int = 1, device: Any = "cuda:0",
                  mode: str = "drone", auto_reset: bool = True, track_episodes: bool = True,
                  wind: Sequence[float] = (0.0, 0.0, 0.0), object_list=(), partitions: int = 1, depth_every: int = 1,
-                 detect_every: int = 1, guided: bool = False, assist: Any = None, assist_sticks: Sequence[float] = (0.0, 0.0, 0.0, 0.0), **batch_options: Any):
+                 detect_every: int = 1, cloud_every: int = 1, guided: bool = False, assist: Any = None, assist_sticks: Sequence[float] = (0.0, 0.0, 0.0, 0.0), **batch_options: Any):
         """`batch_options` go to DroneBatch / RacerBatch (stick_noise=, noise_seed=, drone_id_offset=,
         fp16_state=, with_obs_aos=, kahan_position=, with_done_bits=, per_drone_physics=, ...); `object_list` is the
         collision world of every step (fpyv_amd.objects); `partitions` > 1 enables step_async / step_wait.  `range_rays=`
@@ -1549,7 +1611,11 @@ class FpvVecEnv:
         `detect_every`-th step are followed by a detection of `object_list`, the gate course and - with own_target=True - the
         drone's own target on the same stream (after the pursuit call; each partition into its columns of the one tensor), `boxes`
         [M, 4, num_envs], `box_depth`, `box_visible` and info["boxes" | "box_depth" | "box_visible"] hold the result;
-        `detect_every=0` never detects by itself - call `detect()`.  `pursuit=` (a fpyv_amd.pursuit.PursuitTask) gives every drone a target of its own: reset() and every
+        `detect_every=0` never detects by itself - call `detect()`.  `cloud_camera=` (a fpyv_amd.splat.PointCloudCamera) adds the
+        point-cloud camera under `depth_every`'s rules: reset() and every `cloud_every`-th step are followed by a render of the point
+        clouds of `object_list` and the gate course on the same stream (each partition into its rows of the one tensor),
+        `points_image` [num_envs, H, W] and info["points_image"] (with centroid=True info["points_centroid"]) hold the result; a lane
+        that auto-reset shows its new episode; `cloud_every=0` never renders by itself - call `render_points()`.  `pursuit=` (a fpyv_amd.pursuit.PursuitTask) gives every drone a target of its own: reset() and every
         step are followed by the pursuit call on the same stream (before the scan and the render), which adds the task's payment
         to `reward` and the episode return; `target_obs` [num_envs, 7], `target_position`, `target_event`, `captures` and
         info["target_obs" | "target_event" | "captures"] hold the result.  With `PursuitTask(guide=...)`, `guided=True` flies
@@ -1585,6 +1651,9 @@ class FpvVecEnv:
         if int(detect_every) < 0:
             raise ValueError("detect_every must be >= 0")
         self.detect_every = int(detect_every)
+        if int(cloud_every) < 0:
+            raise ValueError("cloud_every must be >= 0")
+        self.cloud_every = int(cloud_every)
         self.obs_dim = 13
         self.action_dim = 4
         self._obs_view = None
@@ -1722,7 +1791,7 @@ class FpvVecEnv:
         return self.batch.ranges
 
     def _sense(self, stepper: _Handle, stream: Optional[torch.cuda.Stream] = None, scan: bool = True, render: bool = True,
-               detect: bool = False) -> None:
+               detect: bool = False, points: bool = False) -> None:
         """The sensors the env was built with after a step or a reset of `stepper` (the batch, or a partition on its own stream):
         the env's collision world and the batch's course as the batch packs them, the columns of `stepper`."""
         b = self.batch
@@ -1735,6 +1804,31 @@ class FpvVecEnv:
         if detect and b.box_rows is not None:
             b._detect_world(self.object_list, stepper._detect)
             stepper._sensor_raw(stepper._L.fpv_detect_boxes, stepper._detect, stream)
+        if points and b.points_image is not None:
+            b._cloud_world(self.object_list, stepper._splat)
+            stepper._sensor_raw(stepper._L.fpv_splat_render, stepper._splat, stream)
+
+    @property
+    def points_image(self) -> Optional[torch.Tensor]:
+        """[num_envs, H, W] the point-cloud camera's images after the last render (None without cloud_camera=)"""
+        return self.batch.points_image
+
+    @property
+    def points_centroid(self) -> Optional[torch.Tensor]:
+        """[num_envs, 2] (x, y) the centroid of the lit pixels, NaN where none is (None without PointCloudCamera(centroid=True))"""
+        return self.batch.points_centroid
+
+    @property
+    def points_lit(self) -> Optional[torch.Tensor]:
+        return self.batch.points_lit
+
+    def render_points(self) -> torch.Tensor:
+        """Render every drone's point-cloud image now, on the caller's stream, ordered after steps in flight like reset; returns
+        `points_image`."""
+        if self.batch.points_image is None:
+            raise ValueError("this env was built without cloud_camera=")
+        self._whole_population(self._sense, self.batch, scan=False, render=False, points=True)
+        return self.batch.points_image
 
     @property
     def depth(self) -> Optional[torch.Tensor]:
@@ -1745,8 +1839,8 @@ class FpvVecEnv:
         """a reset() is followed by a scan and (unless depth_every / detect_every = 0) a render and a detection of the whole
         population and restarts the counts of steps"""
         for stepper in [self.batch] + self._parts:
-            stepper._depth_steps = stepper._detect_steps = 0
-        self._sense(self.batch, render=bool(self.depth_every), detect=bool(self.detect_every))
+            stepper._depth_steps = stepper._detect_steps = stepper._cloud_steps = 0
+        self._sense(self.batch, render=bool(self.depth_every), detect=bool(self.detect_every), points=bool(self.cloud_every))
 
     def _sense_after_step(self, stepper: _Handle, stream: Optional[torch.cuda.Stream] = None) -> None:
         """every step of `stepper` is followed by the pursuit call (a batch built with pursuit=), then by a scan, every
@@ -1761,7 +1855,11 @@ class FpvVecEnv:
         if self.batch.box_rows is not None and self.detect_every:
             stepper._detect_steps += 1
             seek = stepper._detect_steps % self.detect_every == 0
-        self._sense(stepper, stream, render=due, detect=seek)
+        splat = False
+        if self.batch.points_image is not None and self.cloud_every:
+            stepper._cloud_steps += 1
+            splat = stepper._cloud_steps % self.cloud_every == 0
+        self._sense(stepper, stream, render=due, detect=seek, points=splat)
 
     def render_depth(self) -> torch.Tensor:
         """Render every drone's image now, on the caller's stream, ordered after steps in flight like reset; returns `depth`."""
@@ -1851,6 +1949,10 @@ class FpvVecEnv:
             m = batch._detect_count
             info["boxes"], info["box_depth"] = batch.box_rows[:m, :, lo:hi], batch.box_depth_rows[:m, lo:hi]
             info["box_visible"] = batch.box_visible_rows[:m, lo:hi]
+        if getattr(batch, "points_image", None) is not None:           # the point-cloud camera: [columns, H, W] after the last render
+            info["points_image"] = batch.points_image[lo:hi]
+            if batch.points_centroid is not None:
+                info["points_centroid"] = batch.points_centroid[lo:hi]
         return info
 
     # -- split phase ------------------------------------------------------------------------------

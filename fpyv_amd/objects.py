@@ -12,8 +12,10 @@ Analytic counterparts of the reference's world classes, keeping only what `handl
 
 The rendering arguments (sizes of point clouds, icosphere subdivision, resolutions) are accepted so the
 reference's own call sites (src/core/simulator.py:53-58, src/utils/generators.py) construct these classes
-unchanged, and are ignored: point clouds and rendering are out of scope (the image-plane bounding boxes of these objects are
-`fpyv_amd.detect`; a Ground's `size` is the one rendering argument they read).  Gates and the
+unchanged, and are KEPT: every class has a `points` property, the reference's own point cloud of the object (fpyv_amd.clouds: the
+deterministic generators; `random=True` has none here - pass raw points), which the point-cloud camera renders (fpyv_amd.splat;
+the image-plane bounding boxes of these objects are `fpyv_amd.detect`).  The step, the range scan and the depth camera keep reading
+the analytic solids only.  Gates and the
 Trail never collide in the reference (components.py:202): `to_rows` skips them, so an `object_list` built by the
 reference's code can be passed as is.  A Gate keeps the reference's plane geometry (normal, calculate_distance) and
 describes itself to the gate-course kernels (`as_gate_row`, fpyv_amd.gates).
@@ -29,7 +31,14 @@ from . import _lib
 
 class Ground:
     def __init__(self, size: float = 0.0, resolution: int = 0, random: bool = False):
-        self.size, self.resolution = size, resolution             # point-cloud arguments: unused
+        self.size, self.resolution, self.random = size, resolution, bool(random)      # the point-cloud arguments (`points`)
+
+    @property
+    def points(self) -> np.ndarray:
+        """[resolution^2, 3] float32: the reference's grid (components.py:662-664)"""
+        _no_random(self)
+        from .clouds import ground_points
+        return ground_points(self.size, self.resolution)
 
     position = property(lambda self: np.zeros(3))                 # components.py:667-669
 
@@ -44,6 +53,14 @@ class Cylinder:
         assert height > 0, "height must be positive"
         self.position = np.asarray(position, dtype=np.float64)
         self.radius, self.height = float(radius), float(height)
+        self.angle_resolution, self.height_resolution, self.random = int(angle_resolution), int(height_resolution), bool(random)
+
+    @property
+    def points(self) -> np.ndarray:
+        """[angle_resolution * height_resolution, 3] float32: the reference's mesh plus the position (components.py:695-708)"""
+        _no_random(self)
+        from .clouds import cylinder_points
+        return cylinder_points(self.position, self.radius, self.height, self.angle_resolution, self.height_resolution)
 
     def as_row(self) -> Tuple[float, ...]:
         p = self.position
@@ -58,18 +75,34 @@ def circular_path(center: Sequence[float], radius: float, resolution: int) -> np
 
 class Target:
     """Sphere target; with `path={"radius": r, "resolution": k}` it follows a circle around its
-    initial position, one path point per `update()` (components.py:741-772).  `nu` (icosphere
-    subdivision of the rendered mesh) is accepted and ignored."""
+    initial position, one path point per `update()` (components.py:741-772).  Its cloud is `vertices` (the unit vertices times
+    the radius, like the reference's) plus the position: `vertices=` [V, 3] gives the unit vertices, the default is this build's own
+    icosphere of subdivision `nu` (fpyv_amd.clouds.icosphere, 10 nu^2 + 2 vertices; None: 1), made when first asked for."""
 
-    def __init__(self, position: Sequence[float], radius: float, nu: Any = None, path: Optional[dict] = None):
+    def __init__(self, position: Sequence[float], radius: float, nu: Any = None, path: Optional[dict] = None, vertices: Any = None):
         if isinstance(nu, dict) and path is None:                 # Target(position, radius, path_dict)
             nu, path = None, nu
+        self.nu = nu
+        self._vertices = None if vertices is None else np.asarray(vertices, dtype=np.float64).reshape(-1, 3) * float(radius)
         self.position = np.asarray(position, dtype=np.float64)
         self.radius = float(radius)
         self._path = circular_path(self.position, **path) if path is not None else None
         self._count = 0
         # what the pursuit task reads (fpyv_amd.pursuit): the centre of the path and its arguments; `_count` is the phase
         self.center, self.path = self.position.copy(), (dict(path) if path is not None else None)
+
+    @property
+    def vertices(self) -> np.ndarray:
+        """[V, 3] float64: the local vertices, unit vertices * radius (components.py:758-759)"""
+        if self._vertices is None:
+            from .clouds import icosphere
+            self._vertices = icosphere(1 if self.nu is None else int(self.nu)) * self.radius
+        return self._vertices
+
+    @property
+    def points(self) -> np.ndarray:
+        """[V, 3]: vertices + position (components.py:760, 765-767)"""
+        return self.vertices + np.asarray(self.position, dtype=np.float64)
 
     def update(self) -> None:
         if self._path is not None:
@@ -90,6 +123,13 @@ class Gate:
 
     def __init__(self, position, rotation_matrix, size, shape: str = "rectangle", resolution: int = 17):
         self.position, self.rotation_matrix, self.size, self.shape = position, rotation_matrix, size, shape
+        self.resolution = int(resolution)
+
+    @property
+    def points(self) -> np.ndarray:
+        """[corners + 1, 3] float32: the reference's corner points, the first one again (components.py:790-809)"""
+        from .clouds import gate_points
+        return gate_points(self.position, self.rotation_matrix, self.size, self.shape_code(), self.resolution)
 
     @property
     def normal(self) -> np.ndarray:
@@ -125,6 +165,11 @@ class Trail:
 
     def __init__(self, trail_length: int = -1):
         self.trail_length = trail_length
+
+
+def _no_random(o: Any) -> None:
+    if getattr(o, "random", False):
+        raise ValueError(f"{type(o).__name__}(random=True) has no point cloud here: pass its points as a raw object with a .points array")
 
 
 def to_rows(object_list) -> Tuple[Tuple[float, ...], ...]:

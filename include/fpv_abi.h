@@ -315,7 +315,7 @@ typedef struct fpv_env* fpv_handle_t;
 int fpv_abi_version(void);
 /* sizeof of the ABI structs as this library was compiled (0 fpv_params_t, 1 fpv_buffers_t, 2 fpv_objects_t,
  * 3 fpv_pid_params_t, 4 fpv_cache_model_t, 5 fpv_gate_course_t, 6 fpv_range_scan_t, 7 fpv_depth_render_t, 8 fpv_chase_t,
- * 10 fpv_pursuit_t, 12 fpv_pns_t, 14 fpv_detect_t, 16 fpv_boxes_t):
+ * 10 fpv_pursuit_t, 12 fpv_pns_t, 14 fpv_detect_t, 16 fpv_boxes_t, 18 fpv_splat_t):
  * lets a foreign-language binding verify its struct declarations at load time */
 int fpv_sizeof(int which);
 /* rows of the state matrix for a mode (FPV_DRONE_ROWS / FPV_RACER_ROWS), or FPV_EINVAL */
@@ -965,6 +965,70 @@ int fpv_detect_boxes(fpv_handle_t h, const fpv_buffers_t* b, const fpv_detect_t*
 /* The kernel's own lane function on the host (no handle, no device): drone i of n at p[i][3] with attitude q[i][4] (wxyz); every
  * pointer of *s is HOST memory. */
 int fpv_detect_eval(const fpv_detect_t* s, int64_t n, const float* p /*[n][3]*/, const float* q /*[n][4] wxyz*/);
+
+/* ---- Point-cloud camera: the reference's splatted depth image of every drone (functions and one struct only - FPV_ABI_VERSION,
+ * fpv_params_t and fpv_buffers_t are those of ABI 9) -------------------------------------------------------------------------------
+ * The reference's Camera.render_depth_image and render_image (components.py:602-629) for N drones: the objects whose projected box
+ * misses the image are pruned (the rule of "Object detections", pixel mode FPV_DETECT_INT, on box[m] shifted by offset[m]); every
+ * point X = point + offset[m] of a kept object goes into the camera frame, c = Rcam^T (X - pcam); it is in front when c.z > 0; its
+ * pixel is (trunc((f c.x) / c.z + W/2), trunc((f c.y) / c.z + H/2)) - truncated toward zero like astype(int), so a coordinate in
+ * (-1, 0) lands in column or row 0 -, accepted when 0 <= u < W and 0 <= v < H; a pixel keeps the smallest c.z that landed in it.
+ * FPV_SPLAT_U8: byte = (uint8)(255 (1 - min(z, max_depth) / max_depth)), a pixel without a point takes max_depth (byte 0);
+ * FPV_SPLAT_METRES: that depth as fp32 (max_depth where no point landed, not clipped otherwise); FPV_SPLAT_MASK: the byte 1 where a
+ * point landed, else 0 (render_image).  centroid / lit (optional): the pixels whose U8 byte at this max_depth is > 0 are lit; lit[i] is
+ * their count, centroid[i] = (sum of their columns / count, sum of their rows / count), NaN NaN with none - the tracker of
+ * simulator.py:102-107.  csrc/fpv_splat.h is the ONE definition the kernel (csrc/fpv_splat.hip: a workgroup is a drone, the z-buffer
+ * W * H words of LDS) and fpv_splat_eval run: the same bits.  It reads p and q only, serves every fp32 handle and leaves the state,
+ * the step counter and the rotation alone. */
+#define FPV_SPLAT_MAX_POINTS (1 << 20)
+enum { FPV_SPLAT_METRES = 0, FPV_SPLAT_U8 = 1, FPV_SPLAT_MASK = 2 };
+enum { FPV_CLOUD_GROUND = 0, FPV_CLOUD_CYLINDER = 1, FPV_CLOUD_GATE = 2 };
+typedef struct fpv_splat {
+    uint32_t struct_size;            /* sizeof(fpv_splat_t) = fpv_sizeof(18) (17 stays "no such struct") */
+    int32_t  width, height;          /* written by fpv_splat_derive, like the three camera fields below: 4..128, W a multiple of 4 */
+    int32_t  encoding;               /* FPV_SPLAT_METRES / _U8 / _MASK */
+    float    max_depth;              /* finite, > 0 */
+    int32_t  object_count;           /* M: 0..FPV_MAX_BOXES */
+    double   focal_length;
+    double   relative_rotation[9];
+    double   relative_position[3];
+    int32_t  first[FPV_MAX_BOXES + 1];   /* object m owns the points first[m] .. first[m + 1] - 1; first[0] = 0, non-decreasing, <= 2^20 */
+    int32_t  _reserved;
+    float    offset[FPV_MAX_BOXES][3];   /* added to every point and to the box of object m (a moving Target: its vertices stay put) */
+    float    box[FPV_MAX_BOXES][6];      /* min x, y, z, max x, y, z of object m's points before the offset: finite, min <= max */
+    const float* points;             /* [3][point_ld] x row, y row, z row; DEVICE for fpv_splat_render, HOST for fpv_splat_eval; 4-byte
+                                        aligned; may be NULL when first[M] = 0; columns at and past first[M] are not read */
+    int64_t  point_ld;               /* >= first[M], multiple of 4 */
+    void*    image;                  /* [n][image_ld] elements (fp32 for METRES, bytes for U8 and MASK), row-major [H][W] inside;
+                                        write-only; DEVICE / HOST like points; 4-byte aligned */
+    int64_t  image_ld;               /* elements per drone: >= W * H, multiple of 4; the padding is not written */
+    float*   centroid;               /* [n][2] (x, y) or NULL; DEVICE / HOST like points; 4-byte aligned; given together with lit */
+    int32_t* lit;                    /* [n] or NULL */
+} fpv_splat_t;
+/* Fills width, height, focal_length, relative_rotation and relative_position of *out with what fpv_chase_derive computes for the
+ * camera, under the depth camera's limits (width and height 4..128, width a multiple of 4); every other field is left alone. */
+int fpv_splat_derive(const fpv_camera_t* camera, fpv_splat_t* out);
+/* The deterministic clouds of the reference (host arithmetic only, double, narrowed once) as fp32 SoA out_points[3][ld]:
+ * FPV_CLOUD_GROUND (components.py:655-664): numbers = {size}, resolutions = {resolution}: the resolution^2 grid at z = 0, x fastest;
+ * FPV_CLOUD_CYLINDER (:697-708): numbers = {x, y, z, radius, height}, resolutions = {angle_resolution, height_resolution}: the mesh,
+ * angle fastest, plus the position; FPV_CLOUD_GATE (:790-805): numbers = {position[3], rotation_matrix[9] row-major, size},
+ * resolutions = {shape (FPV_GATE_*), resolution}: the corner points and the first one again.  Returns the number of points (with
+ * out_points NULL nothing is written: a query), or FPV_EINVAL / FPV_EPARAM: a null argument, an unknown kind or shape, a resolution
+ * below 1 (1 gives the start value of the reference's linspace), more points than FPV_SPLAT_MAX_POINTS or than ld, ld not a multiple
+ * of 4, numbers that are not finite. */
+int fpv_cloud_derive(int kind, const double* numbers, const int32_t* resolutions, float* out_points, int64_t ld);
+/* One image per drone of the handle at b->state / b->ld on `stream`, under the handle's device: allocates nothing, never
+ * synchronises, does not advance the step index and does not touch the rotation.  The struct is checked before the handle is
+ * looked at.  FPV_EINVAL / FPV_EALIGN / FPV_EPARAM, by name: null or misaligned pointers, width or height outside 4..128 or width not
+ * a multiple of 4, image_ld < W * H or not a multiple of 4, point_ld < first[M] or not a multiple of 4, object_count outside
+ * 0..FPV_MAX_BOXES, first not starting at 0, decreasing or past 2^20, a box or an offset that is not finite or a box with min > max,
+ * camera numbers that are not fpv_splat_derive's, max_depth not finite or not positive, an unknown encoding, centroid without lit or
+ * lit without centroid, fp16 state; FPV_ENODEV for a null handle where there is no device; and in a library built without
+ * csrc/fpv_splat.hip. */
+int fpv_splat_render(fpv_handle_t h, const fpv_buffers_t* b, const fpv_splat_t* s, void* stream);
+/* The kernel's own point and pixel functions on the host (no handle, no device): drone i of n at p[i][3] with attitude q[i][4]
+ * (wxyz); every pointer of *s is HOST memory. */
+int fpv_splat_eval(const fpv_splat_t* s, int64_t n, const float* p /*[n][3]*/, const float* q /*[n][4] wxyz*/);
 
 const char* fpv_last_error(void);
 const char* fpv_error_name(int code);
