@@ -23,7 +23,8 @@ from typing import Any, Dict, Optional, Sequence, Tuple
 import numpy as np
 import torch
 
-from . import _lib
+from . import _lib, attach
+from .laws import GuidanceLaws
 from .params import DroneParams, MODE_DRONE, MODE_RACER, load_params
 
 
@@ -53,6 +54,7 @@ class _Handle:
 
     _coerce = True              # the single batch turns any stick argument into [n, 4] float32 rows; a partition does not
     _warned_cast = False
+    _handle = None              # (what close() finds when fpv_create was never reached)
 
     def __init__(self, params: DroneParams, n: int, device: torch.device, dev_index: int, auto_reset: bool,
                  pack_kw: Dict[str, Any]):
@@ -71,9 +73,7 @@ class _Handle:
         self._ashape = torch.Size((n, 4))
         self._keepalive = self._last_action = self._bcast_action = None
         self._last_action_ptr = 0
-        self._depth_steps = 0           # steps since the last reset() of the env (FpvVecEnv.depth_every)
-        self._detect_steps = 0          # the same count for FpvVecEnv.detect_every
-        self._cloud_steps = 0           # ... and for FpvVecEnv.cloud_every
+        self._structs, self._sensed = [], 0     # every attachment's struct for this stepper's columns; its steps since the env's last reset()
 
     def _pack(self, params: DroneParams, auto_reset: bool) -> _lib.FpvParams:
         return _lib.pack_params(params, auto_reset=auto_reset, **self._pack_kw)
@@ -95,7 +95,7 @@ class _Handle:
         self._steps_launched = int(step)
 
     def close(self) -> None:
-        if getattr(self, "_handle", None) is not None and self._handle.value:
+        if self._handle is not None and self._handle.value:
             self._L.fpv_destroy(self._handle)
             self._handle = C.c_void_p()
 
@@ -215,11 +215,6 @@ class _Handle:
     def _depth_render_raw(self, render: "_lib.FpvDepthRender", stream: Optional[torch.cuda.Stream] = None) -> None:
         self._sensor_raw(self._L.fpv_depth_render, render, stream)
 
-    def _pursuit_step_raw(self, stream: Optional[torch.cuda.Stream] = None) -> None:
-        """The pursuit call after a step of this handle's drones (fpv_pursuit_step): targets advanced, distance paid, captures
-        respawned, the target observed and - with guide= - the next step's override written"""
-        self._sensor_raw(self._L.fpv_pursuit_step, self._pursuit, stream)
-
     def _pursuit_reset_raw(self, what: "_lib.FpvPursuit", mask: Optional[torch.Tensor]) -> None:
         """The pursuit call after a reset of the lanes of `mask` (fpv_pursuit_reset), on torch's current stream"""
         rc = self._L.fpv_pursuit_reset(self._handle, self._buf_ref, C.byref(what), mask.data_ptr() if mask is not None else None, self._stream())
@@ -234,8 +229,8 @@ class _Handle:
         return wide
 
 
-class _Batch(_Handle):
-    """Owns the SoA state tensor and the C handle of one shard of drones on one GPU."""
+class _Batch(_Handle, GuidanceLaws):
+    """Owns the SoA state tensor and the C handle of one shard of drones on one GPU, and what is attached to them (`attachments`)."""
 
     def __init__(self, params: DroneParams, num_envs: int, device: Any = "cuda:0", auto_reset: bool = False,
                  track_episodes: bool = False, with_accel: bool = False, with_done_bits: bool = False,
@@ -312,34 +307,15 @@ class _Batch(_Handle):
             # (the library refuses the table on a Racer or fp16-state handle here, and with Kahan rows, the guidance override or
             # the AoS head at the launch that combines them - each by name)
             _lib.check(self._L.fpv_set_physics(self._handle, self.physics.data_ptr(), self.ld))
-        # the range sensor (fpv_range_scan): `range_rays` [R, 3] unit body-frame directions (fpyv_amd.rays.derive of what was given),
-        # `range_rows` [R, ld] the rows a scan writes - an output: checkpoints do not carry them
-        self.range_rays = self.range_rows = self._scan = None
-        if range_rays is not None:
-            from . import rays as _rays
-            self.range_rays = _rays.derive(range_rays)
-            self.range_rows = torch.zeros((self.range_rays.shape[0], self.ld), **f32)
-            self._scan = _lib.pack_range_scan(self.range_rays, range_max)
-            self._scan.ranges, self._scan.ranges_ld = self.range_rows.data_ptr(), self.ld
-        # the depth camera (fpv_depth_render): `depth_camera` a fpyv_amd.camera.DepthCamera, `depth` [num_envs, H, W] float32 or
-        # uint8 the images a render writes - caller-visible, zero-copy, an output: checkpoints do not carry them
-        self.depth_camera = self.depth = self._render = None
-        if depth_camera is not None:
-            self.depth_camera = depth_camera
-            self._render = depth_camera.derive()
-            w, h = depth_camera.resolution
-            self.depth = torch.zeros((self.n, h, w), dtype=torch.uint8 if depth_camera.encoding == "u8" else torch.float32, device=self.device)
-            self._render.image, self._render.image_stride = self.depth.data_ptr(), w * h
         self._objects = None            # the address the steps' world is bound at (None = no collision world bound)
-        # the packed tables of the steps' world and of the lists a scan / a render is given (a world that did not move is not re-packed)
-        self._step_table, self._scan_table, self._render_table = _lib.ObjectTable(), _lib.ObjectTable(), _lib.ObjectTable()
-        self._override_keep = None
-        self._done_bits_keep = None
+        self._step_table = _lib.ObjectTable()           # its packed table (a world that did not move is not re-packed)
+        self._override_keep = self._done_bits_keep = None
         self._fill_buffers()
+        self._init_laws()
         # a gate course (fpv_set_gates): the race state is one word per drone, `gate_word`; `gate_desc` holds the descriptor rows
         # of up to 64 gates, `gate_obs_rows` [6, ld] the optional observation rows, `gate_start` [n] the optional start gates
-        self.gate_word = self.gate_desc = self.gate_obs_rows = self.gate_start = None
-        self._course = self._course_kw = None
+        self.gate_word = self.gate_desc = self.gate_obs_rows = self.gate_start = self._course = self._course_kw = None
+        self._gate_list, self.attachments = [], []      # the gates as `set_gates` last left them (None: a checkpoint's, not known); see below
         if gates is not None:
             i32 = dict(dtype=torch.int32, device=self.device)
             self.gate_desc = torch.zeros((_lib.FPV_MAX_GATES, _lib.FPV_GATE_FLOATS), **f32)
@@ -352,29 +328,24 @@ class _Batch(_Handle):
                 self.gate_word = torch.zeros(self.n, **i32)
             self._course_kw = dict(laps=int(laps), gate_rewards=dict(gate_rewards or {}), miss_is_done=bool(miss_is_done))
             self.set_gates(gates)
-        # the pursuit task (fpv_pursuit_step; fpyv_amd.pursuit.PursuitTask): `target_rows` [8, ld] a target per drone (read and written
-        # by the call after every step and reset), `target_obs_rows` [7, ld], `target_position_rows` [3, ld], `target_event_u8` [n] and
-        # `pursuit_reward` [n] its outputs; with guide= `pursuit_pid_rows` [4, ld] and `pursuit_guidance` = (rotation_matrix
-        # [n, 3, 3], thrust_force [n]) of the last call, in the layout the step's override reads
-        self.pursuit = pursuit
-        self.target_rows = self.target_obs_rows = self.target_position_rows = self.target_event_u8 = self.pursuit_reward = None
-        self.pursuit_pid_rows = self.pursuit_guidance = self._pursuit = self._pursuit_set = self._pursuit_chase = None
-        if pursuit is not None:
-            self._init_pursuit(pursuit)
-        # the object detections (fpv_detect_boxes; fpyv_amd.detect.BoxDetector): `box_rows` [slots, 4, ld], `box_depth_rows` [slots, ld]
-        # and `box_visible_rows` [slots, ld] bool the rows a detection writes - outputs: checkpoints do not carry them.  `detect_slots`
-        # is how many boxes the rows hold: by default the most an object list can bring (8), the gates of the course the batch is
-        # built with and the own-target slot
-        self.detector = detector
-        self.box_rows = self.box_depth_rows = self.box_visible_rows = self._detect = None
-        if detector is not None:
-            self._init_detector(detector, detect_slots)
-        # the point-cloud camera (fpv_splat_render; fpyv_amd.splat.PointCloudCamera): `points_image` [num_envs, H, W] uint8 or float32
-        # and - PointCloudCamera(centroid=True) - `points_centroid` [num_envs, 2], `points_lit` [num_envs]: outputs, not in checkpoints
-        self.cloud_camera = cloud_camera
-        self.points_image = self.points_centroid = self.points_lit = self._splat = None
-        if cloud_camera is not None:
-            self._init_cloud_camera(cloud_camera)
+        self.pursuit, self.depth_camera, self.detector, self.cloud_camera = pursuit, depth_camera, detector, cloud_camera
+        self._detect_count, self._cloud, self._cloud_dev = 0, None, None       # (attach: the last detection's boxes, the last cloud, its upload)
+
+        def of(a, *names):              # the tensors of an attachment (fpyv_amd.attach describes them) under the batch's public names
+            return [None if a is None else getattr(a, k) for k in names]
+        self._pursuit = None if pursuit is None else attach.Pursuit(self, pursuit)
+        (self.target_rows, self.target_obs_rows, self.target_position_rows, self.target_event_u8, self.pursuit_reward, self.pursuit_pid_rows,
+         self.pursuit_guidance) = of(self._pursuit, "rows", "obs_rows", "position_rows", "event", "reward", "pid_rows", "guidance")
+        self._range_sensor = None if range_rays is None else attach.RangeSensor(self, range_rays, range_max)
+        self.range_rays, self.range_rows, self._scan = of(self._range_sensor, "rays", "rows", "struct")
+        self._depth_sensor = None if depth_camera is None else attach.DepthSensor(self, depth_camera)
+        self.depth, self._render = of(self._depth_sensor, "image", "struct")
+        self._box_sensor = None if detector is None else attach.BoxSensor(self, detector, detect_slots)
+        self.box_rows, self.box_depth_rows, self.box_visible_rows, self._detect = of(self._box_sensor, "rows", "depth_rows", "visible_rows", "struct")
+        self._cloud_sensor = None if cloud_camera is None else attach.CloudSensor(self, cloud_camera)
+        self.points_image, self.points_centroid, self.points_lit, self._splat = of(self._cloud_sensor, "image", "centroid", "lit", "struct")
+        self.attachments = [a for a in (self._pursuit, self._range_sensor, self._depth_sensor, self._box_sensor, self._cloud_sensor) if a is not None]
+        self._structs = [a.struct for a in self.attachments]
 
     # -- plumbing ---------------------------------------------------------------------------------
     def _fill_buffers(self) -> None:
@@ -476,7 +447,7 @@ class _Batch(_Handle):
         rounds and differs between devices)."""
         d: Dict[str, Any] = {}
         for k in self._CKPT_TENSORS:
-            t = getattr(self, k, None)
+            t = getattr(self, k)
             if t is None:
                 continue
             if k in self._CKPT_ROW_TENSORS:
@@ -525,7 +496,7 @@ class _Batch(_Handle):
         for k in self._CKPT_TENSORS:
             if k not in d:
                 continue
-            mine, src = getattr(self, k, None), d[k]
+            mine, src = getattr(self, k), d[k]
             if mine is None:
                 raise ValueError(f"checkpoint has {k!r} but this batch was built without it")
             if k in self._CKPT_ROW_TENSORS:
@@ -558,13 +529,15 @@ class _Batch(_Handle):
             if self._course is None or kw != self._course_kw or count != int(self._course.count):
                 self._course_kw = kw
                 self._bind_course(count)
-            if self._detect is not None:
+            if self._box_sensor is not None:
                 # a checkpoint holds the descriptor rows, not the gates: unless they are the rows of the gates this batch knows, the
-                # next detection has nothing to box them from and says so (`_detect_world`) until set_gates() is called
+                # next detection has nothing to box them from and says so (`attach.BoxSensor.bind`) until set_gates() is called
                 from . import gates as _gates
                 known = self._gate_list or []
                 same = len(known) == count and np.array_equal(_gates.derive(known), self.gate_desc[:count].cpu().numpy())
-                self._gate_list, self._detect_key = (known if same else None), None
+                self._gate_list = known if same else None
+            for a in self.attachments:
+                a.world_changed()
         self.set_step_counter(d["step_counter"])
 
     # -- gate courses ------------------------------------------------------------------------------
@@ -585,15 +558,15 @@ class _Batch(_Handle):
         a moving Target is re-bound.  Needs a batch built with gates=."""
         if self.gate_word is None:
             raise ValueError("this batch was built without gates=")
+        from . import gates as _gates
+        rows = None if gates is None else _gates.derive(gates)
+        self._gate_list = list(gates or ())     # what a detection boxes and the point-cloud camera splats: the gates as they stand now
+        for a in self.attachments:
+            a.world_changed()
         if gates is None:
             _lib.check(self._L.fpv_set_gates(self._handle, None))
             self._course = None
-            self._gate_list, self._detect_key, self._cloud_key = [], None, None
             return
-        from . import gates as _gates
-        rows = _gates.derive(gates)
-        self._gate_list = list(gates)                       # what a detection boxes (fpyv_amd.detect): the gates as they stand now
-        self._detect_key = self._cloud_key = None           # ... and what the point-cloud camera splats (fpyv_amd.splat)
         self.gate_desc[:rows.shape[0]].copy_(torch.from_numpy(rows))
         if self._course is None or int(self._course.count) != rows.shape[0]:
             self._bind_course(rows.shape[0])
@@ -619,40 +592,11 @@ class _Batch(_Handle):
         return None if self.gate_obs_rows is None else self.gate_obs_rows[:, :self.n].t()
 
     # -- pursuit task ------------------------------------------------------------------------------
-    def _init_pursuit(self, task) -> None:
-        f32 = dict(dtype=torch.float32, device=self.device)
-        self.target_rows = torch.from_numpy(task.rows(self.n, self.ld)).to(self.device)
-        self._pursuit_circle = torch.from_numpy(task.circle).to(self.device)
-        self.target_position_rows = torch.zeros((3, self.ld), **f32)
-        self.target_event_u8 = torch.zeros(self.n, dtype=torch.uint8, device=self.device)
-        self.pursuit_reward = torch.zeros(self.n, **f32)
-        s = task.derive(self.params.dt)
-        s.targets, s.targets_ld, s.circle = self.target_rows.data_ptr(), self.ld, self._pursuit_circle.data_ptr()
-        s.position, s.position_ld = self.target_position_rows.data_ptr(), self.ld
-        s.event, s.reward_out = self.target_event_u8.data_ptr(), self.pursuit_reward.data_ptr()
-        if task.obs:
-            self.target_obs_rows = torch.zeros((_lib.FPV_PURSUIT_OBS, self.ld), **f32)
-            s.obs, s.obs_ld = self.target_obs_rows.data_ptr(), self.ld
-        g = task.chase(self.params)
-        if g is not None:
-            self.pursuit_pid_rows = torch.zeros((_lib.FPV_PID_ROWS, self.ld), **f32)
-            self.pursuit_pid_rows[_lib.FPV_PID_ROWS - 1] = 1.0                  # is_first: a freshly reset PID
-            self.pursuit_guidance = (torch.zeros((self.n, 3, 3), **f32), torch.full((self.n,), float("nan"), **f32))
-            g.pid_state, g.pid_ld = self.pursuit_pid_rows.data_ptr(), self.ld
-            g.rotation, g.thrust = self.pursuit_guidance[0].data_ptr(), self.pursuit_guidance[1].data_ptr()
-            self._pursuit_chase = g
-            s.guide = C.pointer(g)
-        self._pursuit = s
-        # set_targets: the same call without a move and without a respawn - it only restarts the distance of the lanes it is given
-        self._pursuit_set = _lib.FpvPursuit.from_buffer_copy(s)
-        self._pursuit_set.advance = self._pursuit_set.respawn_on_done = 0
-
     def set_targets(self, targets, mask=None) -> None:
         """New targets for the drones of `mask` (None = all): what `PursuitTask(targets=)` takes, one per drone or one for all.
         Their rows are uploaded on torch's current stream and the lanes rebase against them (fpv_pursuit_reset without a move or a
         respawn): no progress is paid across the change, the episode's captures restart, a guide's PID restarts."""
-        if self._pursuit is None:
-            raise ValueError("this batch was built without pursuit=")
+        attach.need(self._pursuit, "batch", "pursuit")
         rows = torch.from_numpy(self.pursuit.rows(self.n, self.ld, targets)).to(self.device)
         m = None
         if mask is not None:
@@ -662,7 +606,7 @@ class _Batch(_Handle):
             cells, mine = rows.view(torch.int32), self.target_rows.view(torch.int32)     # (words: COUNT and SPAWNS are no floats)
             cells[:, :self.n] = torch.where(m.bool(), cells[:, :self.n], mine[:, :self.n])
         self.target_rows.copy_(rows)
-        self._pursuit_reset_raw(self._pursuit_set, m)
+        self._pursuit_reset_raw(self._pursuit.rebase, m)
         self._keepalive_targets = m
 
     @property
@@ -704,7 +648,7 @@ class _Batch(_Handle):
                                      self._stream()))
         self._keepalive_reset = (pos, vel, ang, m)
         if self._pursuit is not None:                   # the targets of the same lanes, after the state on the same stream
-            self._pursuit_reset_raw(self._pursuit, m)
+            self._pursuit_reset_raw(self._pursuit.struct, m)
 
     # -- per-drone physics ------------------------------------------------------------------------
     def _upload_physics(self, rows: np.ndarray, mask) -> None:
@@ -759,26 +703,17 @@ class _Batch(_Handle):
             at = at if self._step_table.rows else None
         self._objects = self._buf.objects = at              # together: `step` reads `_objects` for "nothing is bound"
 
-    def _sensor_world(self, table: "_lib.ObjectTable", object_list) -> Optional[int]:
-        """Where the object list of the next scan or render is: given, it is converted as `step` converts it into the sensor's own
-        `table` (nothing is bound to the steps: a Racer can see a world it does not collide with); None takes what `set_objects`
-        or the last `step` bound, the empty list if nothing is."""
-        return self._buf.objects if object_list is None else table.address(object_list)
-
-    # -- range sensor ------------------------------------------------------------------------------
-    def _scan_world(self, object_list, scan: Optional["_lib.FpvRangeScan"] = None) -> None:
-        """The object list of the next scan (`_sensor_world`) into `scan`: this batch's, or a partition's copy of it."""
-        if self._scan is None:
-            raise ValueError("this batch was built without range_rays=")
-        (self._scan if scan is None else scan).objects = self._sensor_world(self._scan_table, object_list)
+    # -- the sensors' public calls and views (fpyv_amd.attach) -----------------------------------------
+    # (the world binding of the next scan / render alone, into the batch's own struct: what a launch with a struct of the caller's needs)
+    _scan_world = lambda self, object_list: self._range_sensor.bind(self, object_list, self._scan)  # noqa: E731
+    _render_world = lambda self, object_list: self._depth_sensor.bind(self, object_list, self._render)  # noqa: E731
 
     def range_scan(self, object_list=None) -> torch.Tensor:
         """One scan of the range sensor on torch's current stream: for every ray of `range_rays` and every drone, the distance
         along the ray (body frame, turned by the drone's attitude) to the nearest Ground / Cylinder / Target of `object_list`,
         at most `range_max`; 0 from inside an object.  Returns `ranges`.  The scan reads the position and the attitude only:
         state, rewards, the step counter and the rotation of the traversal are what they were (include/fpv_abi.h "Range scan")."""
-        self._scan_world(object_list)
-        self._range_scan_raw(self._scan)
+        attach.need(self._range_sensor, "batch", "range_rays").run(self, object_list)
         return self.ranges
 
     @property
@@ -786,69 +721,14 @@ class _Batch(_Handle):
         """[R, num_envs] view of the range rows as the last scan wrote them (`.T`: the [num_envs, R] block of an observation)"""
         return None if self.range_rows is None else self.range_rows[:, :self.n]
 
-    # -- depth camera ------------------------------------------------------------------------------
-    def _render_world(self, object_list, render: Optional["_lib.FpvDepthRender"] = None) -> None:
-        """The object list (`_sensor_world`) and the gates of the next render into `render`: this batch's, or a partition's copy
-        of it.  A batch with a bound course passes its own descriptor table: gates that `set_gates` moved are seen where they are."""
-        if self._render is None:
-            raise ValueError("this batch was built without depth_camera=")
-        r = self._render if render is None else render
-        course = getattr(self, "_course", None)
-        r.gate_count = int(course.count) if course is not None else 0
-        r.gate_descriptors = self.gate_desc.data_ptr() if course is not None else None
-        r.objects = self._sensor_world(self._render_table, object_list)
-
     def render_depth(self, object_list=None) -> torch.Tensor:
         """One image per drone on torch's current stream: what the drone's `depth_camera` sees of the Ground / Cylinder / Target
         entries of `object_list` and of the batch's gate course - per pixel the z-depth of the nearest one, at most the camera's
         `max_depth`; 0 from inside an object.  Returns `depth` [num_envs, H, W].  The render reads the position and the attitude
         only: state, rewards, the step counter and the rotation of the traversal are what they were (include/fpv_abi.h "Depth
         camera")."""
-        self._render_world(object_list)
-        self._depth_render_raw(self._render)
+        attach.need(self._depth_sensor, "batch", "depth_camera").run(self, object_list)
         return self.depth
-
-    # -- object detections -------------------------------------------------------------------------
-    def _init_detector(self, det, slots: Optional[int]) -> None:
-        own = bool(det.own_target)
-        if own and self._pursuit is None:
-            raise ValueError("BoxDetector(own_target=True) needs a batch built with pursuit=: the slot is the drone's own target")
-        cap = int(slots) if slots is not None else _lib.FPV_MAX_OBJECTS + len(getattr(self, "_gate_list", None) or ()) + int(own)
-        if not 1 <= cap <= _lib.FPV_MAX_BOXES:
-            raise ValueError(f"detect_slots must be 1..{_lib.FPV_MAX_BOXES}")
-        f32 = dict(dtype=torch.float32, device=self.device)
-        self.box_rows = torch.zeros((cap, 4, self.ld), **f32)
-        self.box_depth_rows = torch.zeros((cap, self.ld), **f32)
-        self.box_visible_rows = torch.zeros((cap, self.ld), dtype=torch.bool, device=self.device)   # the kernel writes exactly 0 or 1
-        s = det.derive()
-        s.boxes, s.box_depth, s.box_visible, s.ld = self.box_rows.data_ptr(), self.box_depth_rows.data_ptr(), self.box_visible_rows.data_ptr(), self.ld
-        if own:
-            s.target_rows, s.target_ld = self.target_position_rows.data_ptr(), self.ld
-            s.target_radius = self.target_rows.data_ptr() + 4 * _lib.TGT_RADIUS * self.ld
-        self._detect, self._detect_slots, self._detect_count = s, cap, 0
-        self._detect_list, self._detect_key, self._detect_table = [], None, None
-
-    def _detect_world(self, object_list, detect: Optional["_lib.FpvDetect"] = None) -> None:
-        """The box table of the next detection into `detect` (this batch's, or a partition's copy of it): the collidable entries of
-        `object_list` (None: the list of the last detection), then the gates of the course as `set_gates` last left them.  A world
-        that did not move is not boxed again."""
-        if self._detect is None:
-            raise ValueError("this batch was built without detector=")
-        if object_list is not None:
-            self._detect_list = list(object_list)
-        from .objects import to_rows
-        if getattr(self, "_course", None) is not None and getattr(self, "_gate_list", ()) is None:
-            raise ValueError("the gate course came from a checkpoint whose gates this batch was not given: call set_gates(gates) before "
-                             "detect() (a checkpoint holds the descriptor rows, which do not say what a detection boxes)")
-        gates = (getattr(self, "_gate_list", None) or []) if getattr(self, "_course", None) is not None else []
-        key = (to_rows(self._detect_list), tuple(float(getattr(o, "size", 0.0) or 0.0) for o in self._detect_list), len(gates))          # (set_gates clears the key)
-        if key != self._detect_key:
-            self._detect_table, self._detect_key = self.detector.table(self._detect_list, gates), key
-        m = int(self._detect_table.count) + int(self.detector.own_target)
-        if m > self._detect_slots:
-            raise ValueError(f"{m} boxes do not fit the {self._detect_slots} slots of this batch: build it with detect_slots={m}")
-        self._detect_count = m
-        (self._detect if detect is None else detect).table = C.addressof(self._detect_table)
 
     def detect(self, object_list=None) -> torch.Tensor:
         """One detection on torch's current stream: for every drone and every box - the Ground / Cylinder / Target entries of
@@ -857,8 +737,7 @@ class _Batch(_Handle):
         and whether the reference's pruning rule keeps it.  Fills `boxes` [M, 4, num_envs], `box_depth` [M, num_envs] and
         `box_visible` [M, num_envs]; returns `boxes`.  It reads the position and the attitude only: state, rewards, the step
         counter and the rotation of the traversal are what they were (include/fpv_abi.h "Object detections")."""
-        self._detect_world(object_list)
-        self._sensor_raw(self._L.fpv_detect_boxes, self._detect, None)
+        attach.need(self._box_sensor, "batch", "detector").run(self, object_list)
         return self.boxes
 
     @property
@@ -876,252 +755,14 @@ class _Batch(_Handle):
         """[M, num_envs] bool view: the boxes the reference's pruned_objects_list keeps"""
         return None if self.box_visible_rows is None else self.box_visible_rows[:self._detect_count, :self.n]
 
-    # -- point-cloud camera ------------------------------------------------------------------------
-    def _init_cloud_camera(self, cam) -> None:
-        s = cam.derive()
-        w, h = cam.resolution
-        self.points_image = torch.zeros((self.n, h, w), dtype=torch.float32 if cam.encoding == "metres" else torch.uint8, device=self.device)
-        s.image, s.image_ld = self.points_image.data_ptr(), w * h
-        if cam.centroid:
-            self.points_centroid = torch.zeros((self.n, 2), dtype=torch.float32, device=self.device)
-            self.points_lit = torch.zeros((self.n,), dtype=torch.int32, device=self.device)
-            s.centroid, s.lit = self.points_centroid.data_ptr(), self.points_lit.data_ptr()
-        self._splat = s
-        self._cloud = self._cloud_key = self._cloud_held = self._cloud_dev = self._cloud_dev_of = None
-
-    def _cloud_world(self, world, splat: Optional["_lib.FpvSplat"] = None) -> None:
-        """The cloud of the next render into `splat` (this batch's, or a partition's copy of it).  `world` a PointCloud: taken as it
-        is.  An object list: its clouds in list order (PointCloud.from_world), then the points of the course's gates as `set_gates`
-        last left them; a list of the same objects as last time is not flattened or uploaded again - only the Targets' offsets are
-        read anew (an object whose points changed in place needs a new list or a PointCloud).  None: the world of the last render,
-        the empty one if there was none."""
-        if self._splat is None:
-            raise ValueError("this batch was built without cloud_camera=")
-        from .clouds import PointCloud
-        if isinstance(world, PointCloud):
-            self._cloud, self._cloud_key = world, None
-        elif world is not None or self._cloud is None:
-            objs = list(world or ())
-            gates = (getattr(self, "_gate_list", None) or []) if getattr(self, "_course", None) is not None else []
-            key = tuple(id(o) for o in objs) + (len(gates),)                    # (set_gates clears the key)
-            if key != self._cloud_key:
-                self._cloud, self._cloud_key, self._cloud_held = PointCloud.from_world(objs, gates), key, objs
-        cloud = self._cloud
-        cloud.refresh()
-        if self._cloud_dev_of is not cloud:
-            # a new tensor every time: a render in flight on another stream keeps reading the one it was given
-            self._cloud_dev, self._cloud_dev_of = torch.from_numpy(cloud.points).to(self.device), cloud
-        s = self._splat if splat is None else splat
-        cloud.fill(s)
-        s.points = self._cloud_dev.data_ptr()
-
     def render_points(self, cloud_or_object_list=None) -> torch.Tensor:
         """One image per drone on torch's current stream: the reference's splatted image (Camera.render_depth_image / render_image)
         of the point clouds of `cloud_or_object_list` - a fpyv_amd.clouds.PointCloud, or an object list whose entries have `points`
         (with the batch's gate course after them); None renders the last world again, a moved Target where it is now.  Returns
         `points_image` [num_envs, H, W]; PointCloudCamera(centroid=True) also fills `points_centroid` and `points_lit`.  The render
         reads the position and the attitude only (include/fpv_abi.h "Point-cloud camera")."""
-        self._cloud_world(cloud_or_object_list)
-        self._sensor_raw(self._L.fpv_splat_render, self._splat, None)
+        attach.need(self._cloud_sensor, "batch", "cloud_camera").run(self, cloud_or_object_list)
         return self.points_image
-
-    # -- target chase ------------------------------------------------------------------------------
-    def _chase_rows(self) -> torch.Tensor:
-        """The [4, ld] guidance-PID rows the law reads and advances: `force_multiplier_pid`'s own state where the batch has one"""
-        pid = getattr(self, "force_multiplier_pid", None)
-        if pid is not None:
-            return pid.state
-        if getattr(self, "_chase_scratch_rows", None) is None:
-            self._chase_scratch_rows = torch.zeros((_lib.FPV_PID_ROWS, self.ld), dtype=torch.float32, device=self.device)
-        return self._chase_scratch_rows
-
-    def set_chase_camera(self, camera=None, max_depth: float = 15.0) -> None:
-        """The camera the target chase looks through - a fpyv_amd.camera.DepthCamera / Camera; None: the params' `camera` section,
-        the reference's 640 x 480 - and the reach within which it sees the target (simulator.py:102: 15).  Takes effect with the
-        next `calculate_needed_force_orientation` / `track` / `point_and_shoot`."""
-        self._chase_camera, self._chase_structs, self._pns_structs = (camera, float(max_depth)), {}, {}
-
-    def _chase(self, pixel, target, ref_frame: str, mode: str, rows: torch.Tensor):
-        """One launch of fpv_chase_guide on torch's current stream into the preallocated outputs"""
-        from .chase import ChaseGuidance, target_row
-        if getattr(self, "_chase_camera", None) is None:
-            self.set_chase_camera()
-        if getattr(self, "_chase_out", None) is None:
-            f32 = dict(dtype=torch.float32, device=self.device)
-            self._chase_out = (torch.zeros((self.n, 3, 3), **f32), torch.zeros(self.n, **f32), torch.zeros((self.n, 2), **f32),
-                               torch.zeros(self.n, dtype=torch.bool, device=self.device))
-        key = (ref_frame, mode)
-        if key not in self._chase_structs:
-            camera, max_depth = self._chase_camera
-            self._chase_structs[key] = ChaseGuidance(self.params, camera=camera, ref_frame=ref_frame, mode=mode, max_depth=max_depth).derive()
-        s = self._chase_structs[key]
-        c, r = target_row(target)
-        s.target[:] = [float(x) for x in c]
-        s.target_radius = r
-        rot, thrust, pix, vis = self._chase_out
-        if rows is not self._chase_rows():            # `track`: the law's outputs of a scratch PID go to scratch tensors
-            if getattr(self, "_chase_track_out", None) is None:
-                self._chase_track_out = (torch.zeros_like(rot), torch.zeros_like(thrust))
-            rot, thrust = self._chase_track_out
-        keep = None
-        if pixel is not None:
-            keep = torch.as_tensor(np.asarray(pixel, dtype=np.float32) if not torch.is_tensor(pixel) else pixel,
-                                   dtype=torch.float32, device=self.device)
-            if keep.shape == (2,):
-                keep = keep.expand(self.n, 2)
-            if keep.shape != (self.n, 2):
-                raise ValueError(f"pixel must be [2] or [{self.n}, 2] in (x, y) order, got {tuple(keep.shape)}")
-            keep = keep.contiguous()
-        s.pixel = keep.data_ptr() if keep is not None else None
-        s.pid_state, s.pid_ld = rows.data_ptr(), rows.shape[1]
-        s.rotation, s.thrust, s.pixel_out, s.visible = rot.data_ptr(), thrust.data_ptr(), pix.data_ptr(), vis.data_ptr()
-        self._sensor_raw(self._L.fpv_chase_guide, s, None)
-        self._chase_keep = keep
-        return rot, thrust, pix, vis
-
-    def calculate_needed_force_orientation(self, pixel, target, ref_frame: str = "world", mode: str = "level"):
-        """Drone.calculate_needed_force_orientation (components.py:258-304) for every drone, one kernel: `pixel` [num_envs, 2]
-        (x, y) where the drone's camera sees `target`, or None = find it (the projection of the target's centre; include/fpv_abi.h
-        "Target chase").  Returns (rotation_matrix [num_envs, 3, 3], thrust_force [num_envs]) in preallocated tensors that the
-        next call overwrites - what `step(..., rotation_matrix=, thrust_force=)` takes as they are.  A drone that does not see the
-        target gets thrust_force NaN (step: not overridden) and an identity matrix.  Uses and advances `force_multiplier_pid`'s
-        state for the drones it guides; `reset(mask)` clears it."""
-        rot, thrust, _, _ = self._chase(pixel, target, ref_frame, mode, self._chase_rows())
-        return rot, thrust
-
-    def track(self, target):
-        """(pixel [num_envs, 2] in (x, y) order, visible [num_envs] bool): where every drone's camera sees the centre of `target`
-        (NaN where it does not) - the pixel alone: no PID is advanced and the outputs of the last
-        `calculate_needed_force_orientation` stay as they are.  It is the same kernel run on scratch PID rows and scratch
-        matrices: a launch of the whole law for its first step, not a kernel of its own."""
-        if getattr(self, "_chase_track_rows", None) is None:
-            self._chase_track_rows = torch.zeros((_lib.FPV_PID_ROWS, self.ld), dtype=torch.float32, device=self.device)
-        _, _, pix, vis = self._chase(None, target, "world", "level", self._chase_track_rows)
-        return pix, vis
-
-    # -- point and shoot ---------------------------------------------------------------------------
-    pns_prev_pixel: Optional[torch.Tensor] = None     # [2, ld] Drone.prev_pixel of every drone (NaN = None), made by the law's first use
-
-    @property
-    def pns_pid_rows(self) -> Optional[torch.Tensor]:
-        """The [4, ld] guidance-PID rows point and shoot advances (None before its first use): a checkpoint's rows"""
-        return None if self.pns_prev_pixel is None else self._chase_rows()
-
-    @property
-    def pns_target_rows(self) -> Optional[torch.Tensor]:
-        """The pursuit task's [3, ld] target positions where point and shoot is in use (else None): an env with assist= reads them
-        BEFORE the step's pursuit call writes them again, so a checkpoint has to carry them"""
-        return None if self.pns_prev_pixel is None else self.target_position_rows
-
-    def _pns_rows(self) -> torch.Tensor:
-        if self.pns_prev_pixel is None:
-            self.pns_prev_pixel = torch.full((2, self.ld), float("nan"), dtype=torch.float32, device=self.device)
-            f32 = dict(dtype=torch.float32, device=self.device)
-            u8 = dict(dtype=torch.uint8, device=self.device)
-            self._pns_out = dict(rotation=torch.zeros((self.n, 3, 3), **f32), thrust=torch.full((self.n,), float("nan"), **f32),
-                                 pixel_velocity=torch.zeros((self.n, 2), **f32), limited=torch.zeros(self.n, **u8),
-                                 visible=torch.zeros(self.n, **u8), throttle=torch.zeros(self.n, **f32))
-        return self.pns_prev_pixel
-
-    def _pns_struct(self, ref_frame: str, mode: str) -> "_lib.FpvPns":
-        from .pns import PointAndShoot
-        if getattr(self, "_chase_camera", None) is None:
-            self.set_chase_camera()
-        key = (ref_frame, mode)
-        if key not in self._pns_structs:
-            camera, max_depth = self._chase_camera
-            self._pns_structs[key] = PointAndShoot(self.params, camera=camera, ref_frame=ref_frame, mode=mode, max_depth=max_depth).derive()
-        return self._pns_structs[key]
-
-    def _pns_launch(self, s: "_lib.FpvPns", pixel, action, target, restart) -> None:
-        """One launch of fpv_pns_guide on torch's current stream into the preallocated outputs: `pixel` None | [n, 2] tensor, `action`
-        None | [n, 4] tensor, `target` None | host float32 [3] array | [3, >= n] device rows, `restart` None | [n] uint8 tensor"""
-        prev, rows = self._pns_rows(), self._chase_rows()
-        out = self._pns_out
-        s.pid_state, s.pid_ld, s.prev_pixel, s.prev_pixel_ld = rows.data_ptr(), rows.shape[1], prev.data_ptr(), prev.shape[1]
-        s.pixel = pixel.data_ptr() if pixel is not None else None
-        s.action = action.data_ptr() if action is not None else None
-        s.restart = restart.data_ptr() if restart is not None else None
-        s.target = s.target_rows = None
-        if isinstance(target, np.ndarray):
-            s.target = target.ctypes.data
-        elif target is not None:
-            s.target_rows, s.target_ld = target.data_ptr(), target.stride(0)
-        s.rotation, s.thrust, s.pixel_velocity = out["rotation"].data_ptr(), out["thrust"].data_ptr(), out["pixel_velocity"].data_ptr()
-        s.limited, s.visible, s.throttle = out["limited"].data_ptr(), out["visible"].data_ptr(), out["throttle"].data_ptr()
-        self._sensor_raw(self._L.fpv_pns_guide, s, None)
-        self._pns_keep = (pixel, action, target, restart)
-
-    def _per_drone(self, x, width: int, what: str) -> torch.Tensor:
-        """[width] or [num_envs, width] -> contiguous float32 [num_envs, width] on the device"""
-        t = torch.as_tensor(np.asarray(x, dtype=np.float32) if not torch.is_tensor(x) else x, dtype=torch.float32, device=self.device)
-        if t.shape == (width,):
-            t = t.expand(self.n, width)
-        if t.shape != (self.n, width):
-            raise ValueError(f"{what} must be [{width}] or [{self.n}, {width}], got {tuple(t.shape)}")
-        return t.contiguous()
-
-    def point_and_shoot(self, pixel, action, ref_frame: str = "world", mode: str = "level", target=None, restart=None):
-        """Drone.point_and_shoot (components.py:312-381) for every drone, one kernel (include/fpv_abi.h "Point and shoot"): `pixel`
-        [num_envs, 2] (x, y) where the drone's camera sees its target, or None = find it: then `target` is a Target or a centre [3]
-        for all drones, or [3, >= num_envs] device rows with a centre per drone (`target_position_rows` of a pursuit task as they
-        are).  `action` [4] or [num_envs, 4]: action[1] where on the image the target is to be held, action[2:] the virtual offset
-        of the target in half-images (action[0] is not used: the reference discards what it feeds); None = zeros.  Returns
-        (rotation_matrix [num_envs, 3, 3], thrust_force [num_envs]) in preallocated tensors that the next call overwrites - what
-        `step(..., rotation_matrix=, thrust_force=)` takes as they are; `pixel_velocity`, `thrust_limited` and `pns_throttle` hold
-        the call's other outputs.  A drone that does not see the target, or whose action is not finite, gets thrust_force NaN
-        (step: not overridden) and an identity matrix.  The reference's thrust-limit loop is taken in closed form.
-        Uses and advances `force_multiplier_pid`'s state and `pns_prev_pixel` for the drones it guides; `restart` [num_envs]
-        flags drones that reset both first; `reset(mask)` clears them."""
-        if ref_frame not in _lib.CHASE_FRAMES:
-            raise ValueError("Unknown reference frame")                          # components.py:343
-        if mode not in _lib.CHASE_MODES:
-            raise ValueError("Unknown mode")                                     # components.py:377
-        pix = None if pixel is None else self._per_drone(pixel, 2, "pixel")
-        act = None if action is None else self._per_drone(action, 4, "action")
-        tgt = None
-        if target is not None:
-            if torch.is_tensor(target) and target.dim() == 2:
-                if target.shape[0] != 3 or target.shape[1] < self.n or target.stride(1) != 1 or target.dtype != torch.float32 or target.device != self._dev:
-                    raise ValueError(f"target rows must be a float32 [3, >= {self.n}] tensor on {self.device} with unit column stride")
-                tgt = target
-            else:
-                c = target.position if hasattr(target, "position") else target
-                tgt = np.ascontiguousarray(np.asarray(c.cpu() if torch.is_tensor(c) else c, dtype=np.float32).reshape(3))
-        elif pix is None:
-            raise ValueError("pixel=None needs target=: a Target, a centre [3] or [3, num_envs] rows")
-        rs = None
-        if restart is not None:
-            rs = torch.as_tensor(restart, device=self.device).to(torch.uint8).contiguous()
-            if rs.shape != (self.n,):
-                raise ValueError("restart must have shape (num_envs,)")
-        self._pns_launch(self._pns_struct(ref_frame, mode), pix, act, tgt, rs)
-        return self._pns_out["rotation"], self._pns_out["thrust"]
-
-    @property
-    def pixel_velocity(self) -> Optional[torch.Tensor]:
-        """[num_envs, 2] Drone.pixel_velocity after the last `point_and_shoot`, pixels per second (NaN where the drone was not guided)"""
-        return None if self.pns_prev_pixel is None else self._pns_out["pixel_velocity"]
-
-    @property
-    def thrust_limited(self) -> Optional[torch.Tensor]:
-        """[num_envs] uint8 of the last `point_and_shoot`: 0 not limited, 1 thrust limit reached, 2 limit out of reach"""
-        return None if self.pns_prev_pixel is None else self._pns_out["limited"]
-
-    @property
-    def pns_throttle(self) -> Optional[torch.Tensor]:
-        """[num_envs] thrust2throttle(thrust_force) of the last `point_and_shoot`, in [-1, 1]"""
-        return None if self.pns_prev_pixel is None else self._pns_out["throttle"]
-
-    def _pns_reset(self, mask) -> None:
-        """Drone.reset (components.py:166-168) for the law's rows: prev_pixel = None for the drones of `mask` (None = all)"""
-        if self.pns_prev_pixel is None:
-            return
-        if mask is None:
-            self.pns_prev_pixel.fill_(float("nan"))
-        else:
-            m = torch.as_tensor(mask, device=self.device).bool()
-            self.pns_prev_pixel[:, :self.n].masked_fill_(m, float("nan"))
 
     def set_done_bits_target(self, target: Any = None, stride_words: int = 0) -> None:
         """Where the kernel writes the bit-packed done mask (one wave ballot per 64 drones):
@@ -1257,74 +898,33 @@ class _Partition(_Handle):
         self.stream = stream if stream is not None else torch.cuda.Stream(device=parent.device)
         super().__init__(parent.params, hi - lo, parent.device, parent._dev_index, parent._auto_reset,
                          dict(parent._pack_kw, drone_id_offset=int(parent._pack_kw["drone_id_offset"]) + lo))
+        self._course = None
         self.rebind()
 
+    # the pointers of fpv_buffers_t that run over the drones, with their bytes per drone (attach.columns)
+    _BUFFER_STEPS = dict(state=4, reward=4, done=1, accel=4, pos_comp=4, noise_state=4, reset_pose=4, ep_return=4, ep_length=4,
+                         last_return=4, last_length=4, action_out=4 * 4, obs_aos=4 * _lib.FPV_OBS_AOS_DIM, state_h=4)
+
     def rebind(self) -> None:
-        """Point this partition's fpv_buffers_t at the parent's tensors (again, after the parent re-bound something)."""
-        pb, b, lo = self.parent._buf, self._buf, self.lo
-        off = lambda base, elem_bytes, per_drone=1: (base + lo * elem_bytes * per_drone) if base else None  # noqa: E731
-        b.state, b.ld = off(pb.state, 4), pb.ld
-        b.reward, b.done = off(pb.reward, 4), off(pb.done, 1)
-        b.done_bits = (pb.done_bits + (lo // 64) * 8) if pb.done_bits else None
-        b.accel, b.pos_comp, b.noise_state = off(pb.accel, 4), off(pb.pos_comp, 4), off(pb.noise_state, 4)
-        b.reset_pose = off(pb.reset_pose, 4)
-        b.ep_return, b.ep_length = off(pb.ep_return, 4), off(pb.ep_length, 4)
-        b.last_return, b.last_length = off(pb.last_return, 4), off(pb.last_length, 4)
-        b.action_out, b.obs_aos = off(pb.action_out, 4, 4), off(pb.obs_aos, 4, _lib.FPV_OBS_AOS_DIM)
+        """Point this partition's fpv_buffers_t, its course and its attachments' structs at the parent's tensors (again, after the
+        parent re-bound something)."""
+        parent, lo = self.parent, self.lo
+        pb, b = parent._buf, attach.columns(parent._buf, self._BUFFER_STEPS, lo, into=self._buf)
+        b.ld, b.rounding_seed, b.objects, b.done_bits_stride = pb.ld, pb.rounding_seed, pb.objects, 0
         b.wind[0], b.wind[1], b.wind[2] = pb.wind[0], pb.wind[1], pb.wind[2]
-        b.rounding_seed, b.objects = pb.rounding_seed, pb.objects
-        if pb.state_h:
-            # fp16 storage: the pair rows move by lo words, the row of thrust halves (two drones per word) by lo halves -
-            # it gets its own pointer (fpv_buffers_t.state_h_thrust)
-            b.state_h = pb.state_h + 4 * lo
-            b.state_h_thrust = pb.state_h + 2 * (2 * _lib.FPV_HALF_PAIR_ROWS * pb.ld + lo)
-        else:
-            b.state_h = b.state_h_thrust = None
-        b.done_bits_stride = 0
-        if self.parent.physics is not None:            # this partition's column range of the one table
-            _lib.check(self._L.fpv_set_physics(self._handle, self.parent.physics.data_ptr() + 4 * lo, pb.ld))
-        pc = getattr(self.parent, "_course", None)     # the parent's course on this partition's columns of the word and obs rows
-        if pc is not None:
-            c = _lib.FpvGateCourse.from_buffer_copy(pc)
-            c.gate_word = pc.gate_word + 4 * lo
-            c.gate_obs = off(pc.gate_obs, 4)
-            c.gate_start = off(pc.gate_start, 1)
-            _lib.check(self._L.fpv_set_gates(self._handle, C.byref(c)))
-            self._course = c
-        elif getattr(self, "_course", None) is not None:
+        b.done_bits = (pb.done_bits + (lo // 64) * 8) if pb.done_bits else None            # a bit per drone
+        # fp16 storage: the pair rows move by lo words, the row of thrust halves (two drones per word) by lo halves -
+        # it gets its own pointer (fpv_buffers_t.state_h_thrust)
+        b.state_h_thrust = (pb.state_h + 2 * (2 * _lib.FPV_HALF_PAIR_ROWS * pb.ld + lo)) if pb.state_h else None
+        if parent.physics is not None:                 # this partition's columns of the one table
+            _lib.check(self._L.fpv_set_physics(self._handle, parent.physics.data_ptr() + 4 * lo, pb.ld))
+        if parent._course is not None:                 # the parent's course on this partition's columns of the word and obs rows
+            self._course = attach.columns(parent._course, dict(gate_word=4, gate_obs=4, gate_start=1), lo)
+            _lib.check(self._L.fpv_set_gates(self._handle, C.byref(self._course)))
+        elif self._course is not None:
             _lib.check(self._L.fpv_set_gates(self._handle, None))
             self._course = None
-        self._scan = None
-        if self.parent._scan is not None:              # the parent's ray set on this partition's columns of the range rows
-            self._scan = _lib.FpvRangeScan.from_buffer_copy(self.parent._scan)
-            self._scan.ranges = self.parent._scan.ranges + 4 * lo
-        self._pursuit = self._pursuit_chase = None
-        pp = getattr(self.parent, "_pursuit", None)    # the parent's pursuit task on this partition's columns of its rows and outputs
-        if pp is not None:
-            t = self._pursuit = _lib.FpvPursuit.from_buffer_copy(pp)
-            t.targets, t.obs, t.position = pp.targets + 4 * lo, off(pp.obs, 4), off(pp.position, 4)
-            t.event, t.reward_out = off(pp.event, 1), off(pp.reward_out, 4)
-            pg = self.parent._pursuit_chase
-            if pg is not None:
-                g = self._pursuit_chase = _lib.FpvChase.from_buffer_copy(pg)
-                g.pid_state, g.rotation, g.thrust = pg.pid_state + 4 * lo, pg.rotation + 36 * lo, pg.thrust + 4 * lo
-                t.guide = C.pointer(g)
-        self._detect = None
-        pd = getattr(self.parent, "_detect", None)     # the parent's detector on this partition's columns of the box rows
-        if pd is not None:
-            d = self._detect = _lib.FpvDetect.from_buffer_copy(pd)
-            d.boxes, d.box_depth, d.box_visible = pd.boxes + 4 * lo, pd.box_depth + 4 * lo, pd.box_visible + lo
-            d.target_rows, d.target_radius = off(pd.target_rows, 4), off(pd.target_radius, 4)
-        self._splat = None
-        ps = getattr(self.parent, "_splat", None)      # the parent's point-cloud camera on this partition's rows of its outputs
-        if ps is not None:
-            c = self._splat = _lib.FpvSplat.from_buffer_copy(ps)
-            c.image = ps.image + lo * ps.image_ld * self.parent.points_image.element_size()
-            c.centroid, c.lit = off(ps.centroid, 8), off(ps.lit, 4)
-        self._render = None
-        if self.parent._render is not None:            # the parent's camera on this partition's rows of the one image tensor
-            r = self._render = _lib.FpvDepthRender.from_buffer_copy(self.parent._render)
-            r.image = self.parent._render.image + lo * r.image_stride * self.parent.depth.element_size()
+        self._structs = [a.columns(lo) for a in parent.attachments]     # ... and its attachments on their outputs' columns
 
 
 def partition_bounds(n: int, parts: int) -> Sequence[Tuple[int, int]]:
@@ -1479,7 +1079,7 @@ class DroneBatch(_Batch):
                 self._buf.rotation_override = self._buf.thrust_override = None
                 self._override_keep = None
         if self._pursuit is not None:
-            self._pursuit_step_raw()
+            self._pursuit.run(self)
         if not return_imu:
             return None
         if not self.fp16_state:
@@ -1598,32 +1198,35 @@ class FpvVecEnv:
                  mode: str = "drone", auto_reset: bool = True, track_episodes: bool = True,
                  wind: Sequence[float] = (0.0, 0.0, 0.0), object_list=(), partitions: int = 1, depth_every: int = 1,
                  detect_every: int = 1, cloud_every: int = 1, guided: bool = False, assist: Any = None, assist_sticks: Sequence[float] = (0.0, 0.0, 0.0, 0.0), **batch_options: Any):
-        """`batch_options` go to DroneBatch / RacerBatch (stick_noise=, noise_seed=, drone_id_offset=,
-        fp16_state=, with_obs_aos=, kahan_position=, with_done_bits=, per_drone_physics=, ...); `object_list` is the
-        collision world of every step (fpyv_amd.objects); `partitions` > 1 enables step_async / step_wait.  `range_rays=`
-        (with `range_max=`) adds the range sensor: every step - and reset() - is followed by a scan of `object_list` on the same
-        stream, `ranges` [R, num_envs] and info["ranges"] hold the result (a lane that auto-reset reports its reset pose's
-        ranges, like `obs`).  `depth_camera=` (a fpyv_amd.camera.DepthCamera) adds the depth camera: reset() and every
-        `depth_every`-th step are followed by a render of `object_list` and the gate course on the same stream (each partition
-        into its rows of the one tensor), `depth` [num_envs, H, W] and info["depth"] hold the result; `depth_every=0` never renders
-        by itself - call `render_depth()`.  With `depth_every=1` the image always belongs to `obs`: a lane that auto-reset shows
-        its reset pose.  `detector=` (a fpyv_amd.detect.BoxDetector) adds the object detections in the same way: reset() and every
-        `detect_every`-th step are followed by a detection of `object_list`, the gate course and - with own_target=True - the
-        drone's own target on the same stream (after the pursuit call; each partition into its columns of the one tensor), `boxes`
-        [M, 4, num_envs], `box_depth`, `box_visible` and info["boxes" | "box_depth" | "box_visible"] hold the result;
-        `detect_every=0` never detects by itself - call `detect()`.  `cloud_camera=` (a fpyv_amd.splat.PointCloudCamera) adds the
-        point-cloud camera under `depth_every`'s rules: reset() and every `cloud_every`-th step are followed by a render of the point
-        clouds of `object_list` and the gate course on the same stream (each partition into its rows of the one tensor),
-        `points_image` [num_envs, H, W] and info["points_image"] (with centroid=True info["points_centroid"]) hold the result; a lane
-        that auto-reset shows its new episode; `cloud_every=0` never renders by itself - call `render_points()`.  `pursuit=` (a fpyv_amd.pursuit.PursuitTask) gives every drone a target of its own: reset() and every
-        step are followed by the pursuit call on the same stream (before the scan and the render), which adds the task's payment
-        to `reward` and the episode return; `target_obs` [num_envs, 7], `target_position`, `target_event`, `captures` and
-        info["target_obs" | "target_event" | "captures"] hold the result.  With `PursuitTask(guide=...)`, `guided=True` flies
-        every step under the override the previous call wrote (`batch.pursuit_guidance`): the reference's chase loop.
+        """`batch_options` go to DroneBatch / RacerBatch (stick_noise=, noise_seed=, drone_id_offset=, fp16_state=, with_obs_aos=,
+        kahan_position=, with_done_bits=, per_drone_physics=, ...); `object_list` is the collision world of every step
+        (fpyv_amd.objects); `partitions` > 1 enables step_async / step_wait.
+        `range_rays=` (with `range_max=`) adds the range sensor: every step - and reset() - is followed by a scan of `object_list`
+        on the same stream, `ranges` [R, num_envs] and info["ranges"] hold the result (a lane that auto-reset reports its reset
+        pose's ranges, like `obs`).
+        `depth_camera=` (a fpyv_amd.camera.DepthCamera) adds the depth camera: reset() and every `depth_every`-th step are followed
+        by a render of `object_list` and the gate course on the same stream (each partition into its rows of the one tensor),
+        `depth` [num_envs, H, W] and info["depth"] hold the result; `depth_every=0` never renders by itself - call `render_depth()`.
+        With `depth_every=1` the image always belongs to `obs`: a lane that auto-reset shows its reset pose.
+        `detector=` (a fpyv_amd.detect.BoxDetector) adds the object detections in the same way: reset() and every `detect_every`-th
+        step are followed by a detection of `object_list`, the gate course and - with own_target=True - the drone's own target on
+        the same stream (after the pursuit call; each partition into its columns of the one tensor), `boxes` [M, 4, num_envs],
+        `box_depth`, `box_visible` and info["boxes" | "box_depth" | "box_visible"] hold the result; `detect_every=0` never detects
+        by itself - call `detect()`.
+        `cloud_camera=` (a fpyv_amd.splat.PointCloudCamera) adds the point-cloud camera under `depth_every`'s rules: reset() and
+        every `cloud_every`-th step are followed by a render of the point clouds of `object_list` and the gate course on the same
+        stream (each partition into its rows of the one tensor), `points_image` [num_envs, H, W] and info["points_image"] (with
+        centroid=True info["points_centroid"]) hold the result; a lane that auto-reset shows its new episode; `cloud_every=0` never
+        renders by itself - call `render_points()`.
+        `pursuit=` (a fpyv_amd.pursuit.PursuitTask) gives every drone a target of its own: reset() and every step are followed by
+        the pursuit call on the same stream (before the scan and the render), which adds the task's payment to `reward` and the
+        episode return; `target_obs` [num_envs, 7], `target_position`, `target_event`, `captures` and info["target_obs" |
+        "target_event" | "captures"] hold the result. With `PursuitTask(guide=...)`, `guided=True` flies every step under the
+        override the previous call wrote (`batch.pursuit_guidance`): the reference's chase loop.
         `assist=` (a fpyv_amd.pns.PointAndShoot, with `pursuit=`) makes the four commands of point and shoot the env's action:
         `step(action [num_envs, 4])` runs the law against `target_position` as the last pursuit call left it, flies the step under
         that override with the sticks `assist_sticks`, then makes the pursuit call as ever; a lane that was reset - by mask or in
-        the kernel - restarts its guidance PID and prev_pixel.  Not with guided=True; not with partitions > 1 (not built)."""
+        the kernel - restarts its guidance PID and prev_pixel. Not with guided=True; not with partitions > 1 (not built)."""
         if assist is not None:
             if batch_options.get("pursuit") is None:
                 raise ValueError("assist= needs pursuit=: the law steers every drone toward its own target")
@@ -1645,15 +1248,13 @@ class FpvVecEnv:
         self.num_envs = self.batch.n
         self.wind = tuple(float(w) for w in wind)
         self.object_list = list(object_list)
-        if int(depth_every) < 0:
-            raise ValueError("depth_every must be >= 0")
-        self.depth_every = int(depth_every)
-        if int(detect_every) < 0:
-            raise ValueError("detect_every must be >= 0")
-        self.detect_every = int(detect_every)
-        if int(cloud_every) < 0:
-            raise ValueError("cloud_every must be >= 0")
-        self.cloud_every = int(cloud_every)
+        every = dict(depth_every=int(depth_every), detect_every=int(detect_every), cloud_every=int(cloud_every))
+        for option, steps in every.items():
+            if steps < 0:
+                raise ValueError(f"{option} must be >= 0")
+            setattr(self, option, steps)
+        for a in self.batch.attachments:                # (one that no option names launches after every step)
+            a.every = every.get(a.option, 1)
         self.obs_dim = 13
         self.action_dim = 4
         self._obs_view = None
@@ -1686,13 +1287,14 @@ class FpvVecEnv:
             b._buf.rotation_override, b._buf.thrust_override = b._pns_out["rotation"].data_ptr(), b._pns_out["thrust"].data_ptr()
         self.guided = bool(guided)
         if self.guided:
-            g = getattr(self.batch, "pursuit_guidance", None)
+            g, b = self.batch.pursuit_guidance, self.batch._buf
             if g is None:
                 raise ValueError("guided=True needs pursuit=PursuitTask(guide=...)")
             # every step reads the override the last pursuit call wrote (what the library refuses to combine with it - a reset
-            # source, fp16 state, a Racer - it refuses at the step, by name)
-            for stepper, lo in [(self.batch, 0)] + [(P, P.lo) for P in self._parts]:
-                stepper._buf.rotation_override, stepper._buf.thrust_override = g[0].data_ptr() + 36 * lo, g[1].data_ptr() + 4 * lo
+            # source, fp16 state, a Racer - it refuses at the step, by name): each partition its drones' matrices and thrusts
+            b.rotation_override, b.thrust_override = g[0].data_ptr(), g[1].data_ptr()
+            for P in self._parts:
+                attach.columns(b, dict(rotation_override=9 * 4, thrust_override=4), P.lo, into=P._buf)
 
     @property
     def obs(self) -> torch.Tensor:
@@ -1731,16 +1333,12 @@ class FpvVecEnv:
             if not isinstance(self.batch, DroneBatch):
                 raise ValueError("position / velocity / ypr are drone-mode reset arguments")
             kw = dict(position=position, velocity=velocity, ypr=ypr)
-        if not self._parts:
-            self.batch.reset(mask=mask, **kw)
-            self._sense_after_reset()
-            return self.obs
         cur = self._caller_waits_for_partitions()      # steps still in flight on the partitions' streams finish first
-        if self.batch._cparams.flags & _lib.FPV_FLAG_RESET_JITTER:
+        if self._parts and self.batch._cparams.flags & _lib.FPV_FLAG_RESET_JITTER:
             # the jitter of an explicit reset is keyed by the step counter: the partitions', which stepped this population
             self.batch.set_step_counter(min(P._steps_launched for P in self._parts))
         self.batch.reset(mask=mask, **kw)              # (the step counters run on, as the unpartitioned batch's does across a reset)
-        self._sense_after_reset()
+        self._sense(self.batch, reset=True)
         self._partitions_wait_for(cur)
         return self.obs
 
@@ -1790,23 +1388,19 @@ class FpvVecEnv:
         [num_envs, R] block a policy concatenates to `obs`"""
         return self.batch.ranges
 
-    def _sense(self, stepper: _Handle, stream: Optional[torch.cuda.Stream] = None, scan: bool = True, render: bool = True,
-               detect: bool = False, points: bool = False) -> None:
-        """The sensors the env was built with after a step or a reset of `stepper` (the batch, or a partition on its own stream):
-        the env's collision world and the batch's course as the batch packs them, the columns of `stepper`."""
-        b = self.batch
-        if scan and b.range_rows is not None:
-            b._scan_world(self.object_list, stepper._scan)
-            stepper._range_scan_raw(stepper._scan, stream)
-        if render and b.depth is not None:
-            b._render_world(self.object_list, stepper._render)
-            stepper._depth_render_raw(stepper._render, stream)
-        if detect and b.box_rows is not None:
-            b._detect_world(self.object_list, stepper._detect)
-            stepper._sensor_raw(stepper._L.fpv_detect_boxes, stepper._detect, stream)
-        if points and b.points_image is not None:
-            b._cloud_world(self.object_list, stepper._splat)
-            stepper._sensor_raw(stepper._L.fpv_splat_render, stepper._splat, stream)
+    def _sense(self, stepper: _Handle, stream: Optional[torch.cuda.Stream] = None, reset: bool = False) -> None:
+        """What the batch has attached, in its order, after a step of `stepper` (the batch, or a partition on its own stream) - each
+        attachment after every `every`-th step since the last reset - or after a reset of the env: the env's collision world and the
+        batch's course as the batch packs them, the columns of `stepper`."""
+        for s in [self.batch] + self._parts if reset else [stepper]:
+            s._sensed = 0 if reset else s._sensed + 1
+        for a, struct in zip(self.batch.attachments, stepper._structs):
+            if a.every and (a.after_reset if reset else stepper._sensed % a.every == 0):
+                a.run(self.batch, self.object_list, stepper, struct, stream)
+
+    def _sense_now(self, attachment: Optional[attach.Attachment], option: str) -> None:
+        """One launch of `attachment` for every drone now, on the caller's stream, ordered after steps in flight like reset"""
+        self._whole_population(attach.need(attachment, "env", option).run, self.batch, self.object_list)
 
     @property
     def points_image(self) -> Optional[torch.Tensor]:
@@ -1825,9 +1419,7 @@ class FpvVecEnv:
     def render_points(self) -> torch.Tensor:
         """Render every drone's point-cloud image now, on the caller's stream, ordered after steps in flight like reset; returns
         `points_image`."""
-        if self.batch.points_image is None:
-            raise ValueError("this env was built without cloud_camera=")
-        self._whole_population(self._sense, self.batch, scan=False, render=False, points=True)
+        self._sense_now(self.batch._cloud_sensor, "cloud_camera")
         return self.batch.points_image
 
     @property
@@ -1835,44 +1427,14 @@ class FpvVecEnv:
         """[num_envs, H, W] the depth images after the last render (None without depth_camera=): float32 metres or uint8"""
         return self.batch.depth
 
-    def _sense_after_reset(self) -> None:
-        """a reset() is followed by a scan and (unless depth_every / detect_every = 0) a render and a detection of the whole
-        population and restarts the counts of steps"""
-        for stepper in [self.batch] + self._parts:
-            stepper._depth_steps = stepper._detect_steps = stepper._cloud_steps = 0
-        self._sense(self.batch, render=bool(self.depth_every), detect=bool(self.detect_every), points=bool(self.cloud_every))
-
-    def _sense_after_step(self, stepper: _Handle, stream: Optional[torch.cuda.Stream] = None) -> None:
-        """every step of `stepper` is followed by the pursuit call (a batch built with pursuit=), then by a scan, every
-        `depth_every`-th since the last reset() by a render"""
-        if stepper._pursuit is not None:
-            stepper._pursuit_step_raw(stream)
-        due = False
-        if self.batch.depth is not None and self.depth_every:
-            stepper._depth_steps += 1
-            due = stepper._depth_steps % self.depth_every == 0
-        seek = False
-        if self.batch.box_rows is not None and self.detect_every:
-            stepper._detect_steps += 1
-            seek = stepper._detect_steps % self.detect_every == 0
-        splat = False
-        if self.batch.points_image is not None and self.cloud_every:
-            stepper._cloud_steps += 1
-            splat = stepper._cloud_steps % self.cloud_every == 0
-        self._sense(stepper, stream, render=due, detect=seek, points=splat)
-
     def render_depth(self) -> torch.Tensor:
         """Render every drone's image now, on the caller's stream, ordered after steps in flight like reset; returns `depth`."""
-        if self.batch.depth is None:
-            raise ValueError("this env was built without depth_camera=")
-        self._whole_population(self._sense, self.batch, scan=False)
+        self._sense_now(self.batch._depth_sensor, "depth_camera")
         return self.batch.depth
 
     def detect(self) -> torch.Tensor:
         """Detect for every drone now, on the caller's stream, ordered after steps in flight like reset; returns `boxes`."""
-        if self.batch.box_rows is None:
-            raise ValueError("this env was built without detector=")
-        self._whole_population(self._sense, self.batch, scan=False, render=False, detect=True)
+        self._sense_now(self.batch._box_sensor, "detector")
         return self.batch.boxes
 
     @property
@@ -1889,9 +1451,6 @@ class FpvVecEnv:
         return self.batch.box_visible
 
     def _whole_population(self, fn, *a, **kw) -> None:
-        if not self._parts:
-            fn(*a, **kw)
-            return
         cur = self._caller_waits_for_partitions()
         fn(*a, **kw)
         self._partitions_wait_for(cur)
@@ -1914,7 +1473,7 @@ class FpvVecEnv:
                           b.done_u8 if b._auto_reset else None)
             action = self._assist_sticks
         self.batch._step_raw(action)
-        self._sense_after_step(self.batch)
+        self._sense(self.batch)
         return self.obs, self.batch.reward, self.batch.done, self._info(self.batch, 0, self.num_envs)
 
     def _bind_world(self, stepper: _Handle) -> None:
@@ -1933,26 +1492,11 @@ class FpvVecEnv:
             whole = lo == 0 and hi == batch.n
             info["episode_return"] = batch.last_return if whole else batch.last_return[lo:hi]
             info["episode_length"] = batch.last_length if whole else batch.last_length[lo:hi]
-        if getattr(batch, "gate_word", None) is not None:              # a gate course: the race state after this step
+        if batch.gate_word is not None:                                # a gate course: the race state after this step
             w = batch.gate_word[lo:hi]
             info["gates_passed"], info["gate_event"] = (w >> 10) & 0x3FFFFF, (w >> 8) & 3
-        if getattr(batch, "target_rows", None) is not None:            # the pursuit task: the target after this step's call
-            if batch.target_obs_rows is not None:
-                info["target_obs"] = batch.target_obs_rows[:, lo:hi].t()
-            info["target_event"] = batch.target_event_u8[lo:hi]
-            info["captures"] = (batch.target_rows[_lib.TGT_SPAWNS, lo:hi].view(torch.int32) >> 16) & 0xFFFF
-        if getattr(batch, "range_rows", None) is not None:             # the range sensor: [R, columns] after this step's scan
-            info["ranges"] = batch.range_rows[:, lo:hi]
-        if getattr(batch, "depth", None) is not None:                  # the depth camera: [columns, H, W] after the last render
-            info["depth"] = batch.depth[lo:hi]
-        if getattr(batch, "box_rows", None) is not None:               # the detections: [M, 4 | -, columns] after the last detection
-            m = batch._detect_count
-            info["boxes"], info["box_depth"] = batch.box_rows[:m, :, lo:hi], batch.box_depth_rows[:m, lo:hi]
-            info["box_visible"] = batch.box_visible_rows[:m, lo:hi]
-        if getattr(batch, "points_image", None) is not None:           # the point-cloud camera: [columns, H, W] after the last render
-            info["points_image"] = batch.points_image[lo:hi]
-            if batch.points_centroid is not None:
-                info["points_centroid"] = batch.points_centroid[lo:hi]
+        for a in batch.attachments:                                    # each one's outputs after its last launch
+            info.update(a.info(batch, lo, hi))
         return info
 
     # -- split phase ------------------------------------------------------------------------------
@@ -1988,7 +1532,7 @@ class FpvVecEnv:
                 P.stream.wait_stream(cur)
         self._bind_world(P)
         P._step_raw(action, stream=P.stream)
-        self._sense_after_step(P, P.stream)
+        self._sense(P, P.stream)
 
     def step_wait(self, part: int, sync: bool = True) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor, Dict[str, Any]]:
         """(obs, reward, done, info) of partition `part` - views of its columns - ordered after its last enqueued step:
@@ -2038,21 +1582,16 @@ class FpvVecEnv:
         return d
 
     def load_state_dict(self, d: Dict[str, Any]) -> None:
-        if not self._parts:
-            self.batch.load_state_dict(d)
-            return
         ctr = d.get("partition_step_counters") or [d["step_counter"]] * len(self._parts)
-        if len(ctr) != len(self._parts):
+        if self._parts and len(ctr) != len(self._parts):
             raise ValueError("checkpoint was taken with a different number of partitions")
-        cur = self._caller_waits_for_partitions()      # a step still in flight must not land on top of the loaded state
-        self.batch.load_state_dict(d)
+        self._whole_population(self.batch.load_state_dict, d)      # a step still in flight must not land on top of the loaded state
         for P, c in zip(self._parts, ctr):
             P.set_step_counter(c)
-        self._partitions_wait_for(cur)
 
     def close(self) -> None:
         for P in self._parts:                          # a handle is destroyed only after its chain has drained
-            if getattr(P, "_handle", None) is not None and P._handle.value:
+            if P._handle is not None and P._handle.value:
                 P.stream.synchronize()
             P.close()
         self.batch.close()
@@ -2061,7 +1600,7 @@ class FpvVecEnv:
         # an env dropped without close(): its tensors go back to the allocator, which knows only the stream they were
         # allocated on - a partition's chain still running on ITS stream must be through before that memory can be handed out again
         try:
-            for P in getattr(self, "_parts", []):
+            for P in self._parts:
                 P.stream.synchronize()
         except Exception:
             pass
