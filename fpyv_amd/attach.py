@@ -75,7 +75,8 @@ class Pursuit(Attachment):
     """fpv_pursuit_step (fpyv_amd.pursuit.PursuitTask): `rows` [8, ld] a target per drone (read and written by the call after every step
     and reset), `obs_rows` [7, ld], `position_rows` [3, ld], `event` [n] and `reward` [n] its outputs; with guide= `pid_rows` [4, ld] and
     `guidance` = (rotation_matrix [n, 3, 3], thrust_force [n]) of the last call, in the layout the step's override reads.  The call
-    after a reset is the batch's own (`_Batch._reset_raw`, with the lanes' mask)."""
+    after a reset is the batch's own (`_Batch._reset_raw`, with the lanes' mask).  A checkpoint carries what the next call or step
+    reads - `rows`, `pid_rows`, `guidance` -, not the outputs."""
     after_reset = False
 
     def __init__(self, batch: Any, task: Any):

@@ -336,6 +336,8 @@ class _Batch(_Handle, GuidanceLaws):
         self._pursuit = None if pursuit is None else attach.Pursuit(self, pursuit)
         (self.target_rows, self.target_obs_rows, self.target_position_rows, self.target_event_u8, self.pursuit_reward, self.pursuit_pid_rows,
          self.pursuit_guidance) = of(self._pursuit, "rows", "obs_rows", "position_rows", "event", "reward", "pid_rows", "guidance")
+        # (a checkpoint's names for the two: with guided=True the next step flies under them)
+        self.pursuit_rotation, self.pursuit_thrust = self.pursuit_guidance or (None, None)
         self._range_sensor = None if range_rays is None else attach.RangeSensor(self, range_rays, range_max)
         self.range_rays, self.range_rows, self._scan = of(self._range_sensor, "rays", "rows", "struct")
         self._depth_sensor = None if depth_camera is None else attach.DepthSensor(self, depth_camera)
@@ -428,7 +430,7 @@ class _Batch(_Handle, GuidanceLaws):
     # -- checkpoint / resume (the reference has none; state is just tensors here) ------------------
     _CKPT_TENSORS = ("state", "state_h", "reward", "done", "ep_return", "ep_length", "last_return",
                      "last_length", "noise_state", "pos_comp", "reset_pose", "physics", "gate_word", "gate_start", "gate_desc",
-                     "target_rows", "pursuit_pid_rows", "pns_pid_rows", "pns_prev_pixel", "pns_target_rows")
+                     "target_rows", "pursuit_pid_rows", "pursuit_rotation", "pursuit_thrust", "pns_pid_rows", "pns_prev_pixel", "pns_target_rows")
     _CKPT_ROW_TENSORS = ("state", "noise_state", "pos_comp", "reset_pose", "physics", "target_rows", "pursuit_pid_rows", "pns_pid_rows",
                          "pns_prev_pixel", "pns_target_rows")        # [rows, ld]: stored as their logical columns [rows, num_envs]
 
@@ -440,8 +442,12 @@ class _Batch(_Handle, GuidanceLaws):
         return raw[:2 * npair * ld].view(npair, ld, 2), raw[2 * npair * ld:2 * npair * ld + ld]
 
     def state_dict(self) -> Dict[str, Any]:
-        """Everything needed to continue a run bit-for-bit: the device tensors (cloned) and the step counter that keys the
-        stick-noise stream / stochastic rounding.  Row tensors are stored as their LOGICAL columns - `state` [rows, num_envs],
+        """Everything the next step reads, so that a run continues bit for bit: the device tensors (cloned) and the step counter that
+        keys the stick-noise stream / stochastic rounding - of the attachments the pursuit task's target rows, its guide's PID rows
+        and the guidance of its last call (`pursuit_rotation` [n, 3, 3], `pursuit_thrust` [n]: with guided=True the next step flies
+        under them), and point and shoot's rows.  What a launch writes and no step reads - the sensors' outputs, the task's
+        observation, event and payment rows - is left out: it is valid again after that attachment's next launch (DESIGN 1
+        "Checkpoints").  Row tensors are stored as their LOGICAL columns - `state` [rows, num_envs],
         the fp16 words as `state_h` [11, num_envs] int16 in storage order (five pair rows interleaved, then thrust) - so a
         checkpoint does not depend on the row stride the writing library chose (fpv_recommended_ld has changed between
         rounds and differs between devices)."""
@@ -471,7 +477,10 @@ class _Batch(_Handle, GuidanceLaws):
 
     def load_state_dict(self, d: Dict[str, Any]) -> None:
         """Accepts this library's checkpoints (logical columns) and those of rounds <= 5 (padded tensors with the writer's own
-        row stride, whatever it was: the stride is read off the tensor's shape)."""
+        row stride, whatever it was: the stride is read off the tensor's shape).  A tensor the checkpoint does not hold stays as it
+        is (an older file has no `pursuit_rotation` / `pursuit_thrust`); one it holds and this batch was built without is refused
+        by name.  The world is the caller's: a moving Target is update()d to where it was, and after a course that is not the one
+        this batch knows `set_gates()` comes before `detect()`."""
         import warnings
         if d["num_envs"] != self.n or d["mode"] != self.mode:
             raise ValueError("checkpoint was taken from a batch of different size or mode")
@@ -1571,23 +1580,47 @@ class FpvVecEnv:
         for P in self._parts:
             P.set_params(params, self.batch._auto_reset)
 
+    def _steppers(self) -> list:
+        return self._parts or [self.batch]
+
     def state_dict(self) -> Dict[str, Any]:
-        """The batch's checkpoint; with partitions the step counters of all of them (they key the stick-noise streams).
-        The clones are ordered after every partition's last enqueued step."""
+        """The batch's checkpoint (`_Batch.state_dict`); with partitions the step counters of all of them (they key the stick-noise
+        streams); and `sensed`, the steps every stepper - the batch, or each partition - has taken since the last reset: the phase
+        of the sensors' cadences (depth_every, detect_every, cloud_every).  The clones are ordered after every partition's last
+        enqueued step."""
         self._caller_waits_for_partitions()
         d = self.batch.state_dict()
         if self._parts:
             d["partition_step_counters"] = [P._steps_launched for P in self._parts]
             d["step_counter"] = min(d["partition_step_counters"])        # what an unpartitioned env continues from
+        d["sensed"] = [int(s._sensed) for s in self._steppers()]
         return d
 
     def load_state_dict(self, d: Dict[str, Any]) -> None:
+        """`_Batch.load_state_dict` for the whole population, ordered after steps in flight like reset; every partition is bound
+        again to what the batch bound (a course of another length), and the cadence phase continues where the checkpoint's was.
+        A checkpoint of an env with another number of partitions gives every stepper the one count its steppers agreed on; one
+        whose partitions had taken different numbers of steps loads only into as many partitions.  A checkpoint without `sensed`
+        (an older library's) leaves the counts as they are.  Sensor outputs are not in a checkpoint: each is valid again after
+        that sensor's next launch - the first step whose count since the reset is a multiple of its cadence."""
         ctr = d.get("partition_step_counters") or [d["step_counter"]] * len(self._parts)
         if self._parts and len(ctr) != len(self._parts):
             raise ValueError("checkpoint was taken with a different number of partitions")
+        steppers, sensed = self._steppers(), d.get("sensed")
+        if sensed is not None:
+            sensed = [int(x) for x in sensed]
+            if len(sensed) != len(steppers):
+                if len(set(sensed)) != 1:
+                    raise ValueError(f"checkpoint key 'sensed': its {len(sensed)} partitions had taken {sensed} steps since the last reset - "
+                                     f"such a checkpoint loads only into an env with {len(sensed)} partitions, not {len(steppers)}")
+                sensed = sensed[:1] * len(steppers)
         self._whole_population(self.batch.load_state_dict, d)      # a step still in flight must not land on top of the loaded state
         for P, c in zip(self._parts, ctr):
             P.set_step_counter(c)
+            P.rebind()                                              # the course the batch bound, as set_gates does
+        if sensed is not None:
+            for s, count in zip(steppers, sensed):
+                s._sensed = count
 
     def close(self) -> None:
         for P in self._parts:                          # a handle is destroyed only after its chain has drained

@@ -8,59 +8,10 @@ import numpy as np
 import pytest
 import torch
 
-from fpyv_amd import load_params
-from fpyv_amd.camera import DepthCamera
-from fpyv_amd.detect import BoxDetector
-from fpyv_amd.env import FpvVecEnv
-from fpyv_amd.objects import Cylinder, Gate, Ground, Target
-from fpyv_amd.pursuit import PursuitTask
-from fpyv_amd.splat import PointCloudCamera
+from attached_env import COLUMNS_LAST, DEV, INFO_KEYS, N, OUTPUTS, VIEWS, env as _env, same as _same, world as _world
 
 pytestmark = pytest.mark.gpu
-DEV = "cuda:0"
-N, STEPS, RESET_AFTER = 384, 7, 3
-# the public tensors of the batch that the sensors and the task write
-OUTPUTS = ("range_rows", "depth", "box_rows", "box_depth_rows", "box_visible_rows", "points_image", "points_centroid", "points_lit",
-           "target_rows", "target_obs_rows", "target_position_rows", "target_event_u8", "pursuit_reward", "pursuit_pid_rows",
-           "gate_word", "gate_obs_rows", "ep_return", "last_return", "last_length")
-# the views of the env
-VIEWS = ("ranges", "depth", "boxes", "box_depth", "box_visible", "points_image", "points_centroid", "points_lit", "target_obs",
-         "target_position", "target_event", "captures", "gate_obs")
-INFO_KEYS = {"episode_return", "episode_length", "gates_passed", "gate_event", "target_obs", "target_event", "captures", "ranges", "depth",
-             "boxes", "box_depth", "box_visible", "points_image", "points_centroid"}
-COLUMNS_LAST = ("ranges", "boxes", "box_depth", "box_visible")           # info entries whose drones are the last axis; the others' the first
-
-
-def _bits(t):
-    a = np.ascontiguousarray(t.cpu().numpy())
-    return a.view({1: np.uint8, 4: np.uint32}[a.dtype.itemsize])
-
-
-def _same(a, b):
-    return a.shape == b.shape and a.dtype == b.dtype and np.array_equal(_bits(a), _bits(b))
-
-
-def _world():
-    target = Target([-5.0, 2.0, 3.0], 0.8, 2, path=dict(radius=3.0, resolution=12))
-    return [Ground(40, 24), Cylinder([4.0, 3.0, 0.0], 1.0, 5.0, 17, 9), target], target
-
-
-def _env(objs, parts, n=N, every=(2, 3, 2)):
-    """(env, start positions, start velocities) of `n` drones with everything attached; `every` = (depth, detect, cloud)_every"""
-    rng = np.random.default_rng(31)
-    gates = [Gate([9.0, -3.0, 3.0], np.eye(3), 2.0, shape="rectangle"), Gate([-8.0, 6.0, 2.5], np.eye(3), 2.0, shape="half_circle")]
-    targets = dict(centre=np.stack([rng.uniform(-6, 6, n), rng.uniform(-6, 6, n), rng.uniform(1, 5, n)], 1).astype(np.float32),
-                   radius=rng.uniform(0.3, 0.8, n).astype(np.float32), path_radius=rng.uniform(0.5, 4.0, n).astype(np.float32),
-                   phase=rng.integers(0, 29, n))
-    task = PursuitTask(targets=targets, path=dict(radius=2.0, resolution=29), capture_distance=0.25, obs=True, guide=dict(max_depth=40.0),
-                       respawn=dict(lo=(-6.0, -6.0, 1.0), hi=(6.0, 6.0, 5.0), radius=(0.3, 0.8), seed=77))
-    env = FpvVecEnv(load_params(fps=250, ceiling=6.0), num_envs=n, device=DEV, auto_reset=True, object_list=objs, gates=gates, partitions=parts,
-                    range_rays=[[1.0, 0.0, 0.0], [0.0, 1.0, 0.0], [0.0, 0.0, -1.0]], depth_camera=DepthCamera(resolution=(8, 4)),
-                    detector=BoxDetector(own_target=True), cloud_camera=PointCloudCamera(resolution=(8, 4), centroid=True), pursuit=task,
-                    depth_every=every[0], detect_every=every[1], cloud_every=every[2])
-    pos = np.stack([rng.uniform(-8, 8, n), rng.uniform(-8, 8, n), rng.uniform(4.0, 5.9, n)], 1).astype(np.float32)
-    vel = np.stack([rng.uniform(-1, 1, n), rng.uniform(-1, 1, n), rng.uniform(2.0, 9.0, n)], 1).astype(np.float32)
-    return env, pos, vel
+STEPS, RESET_AFTER = 7, 3
 
 
 def _whole(env, one, what):
